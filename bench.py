@@ -1,7 +1,19 @@
 """Benchmark of the MI355X Enhanced-UNet training step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it builds the model and the inputs, runs the
+W warm-up steps, times the K steps, writes the outputs of the last timed step if --dump-outputs is given
+and prints the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step; the roofline and the
+per-step spread come from events the timed region records anyway).  Every leg that takes a run of its own
+(the busy pass of steps_diag, dp_world1, fp32_configs1, dual_configs4, cpu_baseline, parity) runs only
+with --full and is null in a plain line; under --full the --no-* options switch single legs off as before.
+
+--dump-outputs DIR writes what a caller of the timed path holds after the last timed step: the loss it
+returned (loss.npy) and the model's state_dict it updated (state.<key>.npy), float32 (int64 counters as
+float64), at most 64 MB in all (write_outputs).  The weights and the synthetic batch are seeded, so two
+builds run with the same arguments see identical inputs and can be compared file by file.
 
 Workload (BASELINE.json configs[2], the metric's config): base_ch=64,
 1x1024x1024 synthetic bright-field tiles, 1-ch -> 2-class, batch 4 per GPU,
@@ -10,7 +22,8 @@ full Trainer step (forward, fused loss, backward, bucketed RCCL all-reduce when
 N>1, clip_grad_norm_, AdamW; the loss stays on the device, as Trainer.train_epoch keeps
 it).  Inputs are resident in HBM before the timed region.  value = images processed by all ranks / max-over-ranks time.
 
-Also reported on the same JSON line:
+Also reported on the same JSON line (with --full only: dp_world1, fp32_configs1, dual_configs4, the
+extra pass of steps_diag, cpu_baseline, parity):
   roofline      -- the dominant kernel family, the conv3x3 implicit-GEMM MFMA kernels (forward,
                    data gradient, weight gradient): algorithmic FLOPs / the wall time any of them
                    ran (union of HIP-event intervals on both streams of the timed region) vs the
@@ -73,6 +86,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=4, help="images per GPU")
     ap.add_argument("--base", type=int, default=64)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the busy pass of steps_diag, dp_world1, "
+                         "fp32_configs1, dual_configs4, cpu_baseline and the parity legs (each with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss and the model state it left "
+                         "as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-size", type=int, default=0,
                     help="CPU baseline sample: 1 warm-up + 3 timed B=1 steps at this size (0: the bench size)")
@@ -319,14 +338,16 @@ def timed_steps(tr, x, m, steps, warmup, world, dev):
         t0 = time.perf_counter()
         marks[0].record()
         host = [time.perf_counter()]
+        last = None
         for i in range(steps):
-            tr.step(x, m, sync_loss=SYNC_LOSS)
+            last = tr.step(x, m, sync_loss=SYNC_LOSS)
             marks[i + 1].record()
             host.append(time.perf_counter())
         torch.cuda.synchronize()
         t1 = time.perf_counter()
     timer.dp = dp.stop_timing() if dp is not None else None
     timer.local_s = t1 - t0
+    timer.last_loss = last  # what the last timed Trainer.step returned (dump_outputs)
     if world > 1:
         dist.barrier()
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
@@ -340,6 +361,46 @@ def timed_steps(tr, x, m, steps, warmup, world, dev):
     timer.alloc = {k: ms1.get(k, 0) - ms0.get(k, 0) for k in ("num_device_alloc", "num_device_free", "num_alloc_retries")}
     timer.alloc["reserved_gb"] = round(ms1.get("reserved_bytes.all.current", 0) / 2 ** 30, 2)
     return float(elapsed.item()), timer
+
+
+DUMP_BUDGET = 64 * 10 ** 6  # bytes of array data --dump-outputs writes at most, all files together
+DUMP_WHOLE = 1024           # arrays up to this many elements are always written whole
+
+
+def write_outputs(out_dir, named, budget=DUMP_BUDGET):
+    """Write each (name, tensor) of `named` as out_dir/<name>.npy: float32 (float64 / integer tensors as
+    float64, exact for the counters a state_dict holds).  If everything fits the budget the arrays keep
+    their shapes.  Otherwise every array above DUMP_WHOLE elements is cut to the same fraction of its
+    flattened elements, at sorted indices drawn without replacement from a generator seeded with 0 -- a
+    function of the array's size alone, so two runs (or two builds) sample the same elements.  Returns
+    the bytes of array data written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = []
+    for name, t in named:
+        t = torch.as_tensor(t).detach()
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        arrs.append((name, t.to("cpu", torch.float64 if wide else torch.float32).numpy()))
+    small = sum(a.nbytes for _, a in arrs if a.size <= DUMP_WHOLE)
+    large = sum(a.nbytes for _, a in arrs if a.size > DUMP_WHOLE)
+    frac = 1.0 if small + large <= budget else max(0.0, (budget - small) / large)
+    written = 0
+    for name, a in arrs:
+        if frac < 1.0 and a.size > DUMP_WHOLE:
+            keep = int(frac * a.size)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    return written
+
+
+def dump_outputs(out_dir, tr, loss):
+    """--dump-outputs: what a caller of the timed path, Trainer.step, holds after the last timed step --
+    the loss it returned and the model it updated in place (parameters and BN buffers, by state_dict key)."""
+    torch.cuda.synchronize()
+    named = [("loss", loss)] + [("state." + k, v) for k, v in tr.model.state_dict().items()]
+    return write_outputs(out_dir, named)
 
 
 def step_spread(timer):
@@ -592,7 +653,9 @@ def main():
         mine = {"rank": rank, "ms_per_step": round(1e3 * timer.local_s / args.steps, 3), **(timer.dp or {})}
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
-    diag = step_record(timer, tr, x, m)
+    if args.dump_outputs and rank == 0:  # before any leg runs further steps on this model
+        dump_outputs(args.dump_outputs, tr, timer.last_loss)
+    diag = step_record(timer, tr, x, m) if args.full else {"step_ms": step_spread(timer)}
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
@@ -602,23 +665,23 @@ def main():
     roof = conv_roofline(args, timer, args.steps, step_flops, elapsed, args.dtype)
     ms_plain = 1e3 * elapsed / args.steps
     dpw1 = None
-    if world == 1 and not args.no_dp_world1 and not args.dual:
+    if args.full and world == 1 and not args.no_dp_world1 and not args.dual:
         dpw1 = dp_world1_leg(args, tr, x, m, dev, ms_plain)
     del tr
     torch.cuda.empty_cache()
     fp32 = None
-    if world == 1 and not args.no_fp32_leg and not args.dual and \
+    if args.full and world == 1 and not args.no_fp32_leg and not args.dual and \
             (args.base, args.size, args.batch, args.dtype) == (64, 1024, 4, "bf16"):
         fp32 = fp32_configs1_leg(args, dev)
     dual4 = None
-    if world == 1 and not args.no_dual_leg and not args.dual and \
+    if args.full and world == 1 and not args.no_dual_leg and not args.dual and \
             (args.base, args.size, args.batch, args.dtype) == (64, 1024, 4, "bf16"):
         dual4 = dual_configs4_leg(args, dev)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
     dice = logits_err = None
-    if args.dice_size > 0 and not args.dual:
+    if args.full and args.dice_size > 0 and not args.dual:
         pmodel = train_parity_model(args, dev)
         logits_err = logits_rel_err_vs_cpu(pmodel, args, dev)
         dice = dice_vs_cpu_ref(pmodel, args, dev)
@@ -632,6 +695,7 @@ def main():
                   "per_rank": per_rank},
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(ms_plain, 3),
         "higher_is_better": True,
         "scaling": "weak",

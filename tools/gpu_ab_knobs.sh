@@ -6,7 +6,7 @@ set -u
 mkdir -p gpurun_out
 TAG=${TAG:-knobs}
 ROUNDS=${ROUNDS:-3}
-ARGS=${ARGS:-"--steps 30 --warmup 5 --no-cpu-baseline --dice-size 0 --no-dp-world1 --no-fp32-leg --no-dual-leg"}
+ARGS=${ARGS:-"--steps 30 --warmup 5 --full --no-cpu-baseline --dice-size 0 --no-dp-world1 --no-fp32-leg --no-dual-leg"}
 IFS='|' read -ra VS <<< "${VARIANTS:-base}"
 out=gpurun_out/ab_${TAG}.jsonl
 : > $out

@@ -17,7 +17,7 @@ f=$(find gpurun_out/prof_${TAG} -name '*kernel_trace.csv' | head -1)
 python3 tools/trace_steps.py "$f" 3 40 > profiles/${R}_step_timeline.txt
 TAG=${TAG}dp bash tools/gpu_dp_trace.sh > gpurun_out/dp_${TAG}_run.log 2>&1 || { echo "dp trace failed"; exit 1; }
 cp gpurun_out/dp_trace_${TAG}dp.txt profiles/${R}_dp_world1_timeline.txt
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_${TAG}.log 2>&1 || { echo "bench failed"; tail -5 gpurun_out/bench_${TAG}.log; exit 1; }
-grep "^{" gpurun_out/bench_${TAG}.log | tail -1 > gpurun_out/bench_${TAG}.json
-cp gpurun_out/bench_${TAG}.json profiles/${R}_bench.json
+log=$(mktemp)
+timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $log 2>&1 || { echo "bench failed"; tail -5 $log; exit 1; }
+grep "^{" $log | tail -1 > profiles/${R}_bench.json
 echo done

@@ -11,6 +11,7 @@ if [ -n "${TESTS:-}" ]; then
   [ $rc -ne 0 ] && { grep -E "^E  " gpurun_out/pytest_${TAG}.log | head -10; exit $rc; }
 fi
 if [ -z "${NO_BENCH:-}" ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS:-}"  # every leg of the line; --no-* arguments still drop single legs
   timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py ${BENCH_ARGS:-} > gpurun_out/bench_${TAG}.log 2>&1
   rc=$?; echo "bench rc=$rc"; [ $rc -ne 0 ] && { tail -5 gpurun_out/bench_${TAG}.log; exit $rc; }
   grep "^{" gpurun_out/bench_${TAG}.log | tail -1 > gpurun_out/bench_${TAG}.json
