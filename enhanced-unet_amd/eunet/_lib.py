@@ -111,6 +111,17 @@ SIGNATURES = {
     "eunet_softmax_crop": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_accumulate": [_f, _f, c_int64, c_int, c_float, c_void_p],
     "eunet_probs_to_mask": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
+    "eunet_pack_masks": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
+    "eunet_pairwise_overlap": [_f, c_int, _f, c_int, c_int64, _f, c_void_p],
+    "eunet_morph_u8": [_f, _f, _f, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "eunet_label_workspace_bytes": [c_int, c_int, POINTER(c_size_t)],
+    "eunet_label_components": [_f, c_int, c_int, _f, _f, _f, c_int, _f, c_void_p],
+    "eunet_outer_perimeter": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
+    "eunet_mask_eq": [_f, c_int, c_int64, c_int64, _f, _f, c_void_p],
+    "eunet_mask_and": [_f, _f, c_int64, _f, _f, c_void_p],
+    "eunet_write_label": [_f, c_int64, c_int, _f, c_void_p],
+    "eunet_relabel_table": [_f, c_int64, _f, c_int, _f, c_void_p],
+    "eunet_expand_labels": [_f, c_int64, _f, c_int, c_int, _f, c_void_p],
     "eunet_fusion_tiles": [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)],
     "eunet_gate_fwd": [_f, _f, c_int, c_int, c_int, c_int, _f, _f, _f, _f, _f, c_void_p],
     "eunet_gate_mid_fwd": [_f, _f, c_int, c_int, c_int, c_int, _f, _f, _f, _f, _f, _f, c_void_p],

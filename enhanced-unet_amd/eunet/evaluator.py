@@ -1,10 +1,13 @@
-"""Drop-in inference path of reference train_eval.Evaluator (semantic part).
+"""Drop-in inference and evaluation path of reference train_eval.Evaluator.
 
     Evaluator(model, device, model_name)                       # train_eval.py:356-363
     ._run_model_single(image [C,h,w]) -> probs [K,h,w]          # train_eval.py:397-417
     ._run_tta_inference(image) -> probs (5-view TTA mean)       # train_eval.py:419-453
     ._convert_probs_to_mask(probs) -> int64 mask [h,w] (numpy)  # train_eval.py:455-568
     .predict_semantic_mask(image) -> int64 mask [h,w] (numpy)   # train_eval.py:570-606
+    .semantic_to_instances(mask, min_area=3)                    # train_eval.py:654-850
+        -> (instance_masks, instance_labels, instance_scores)
+    .evaluate(dataloader) -> mean semantic / instance / viability rows   # train_eval.py:852-1021
     .evaluate_semantic(dataloader) -> mean semantic metrics     # train_eval.py:852-904 (semantic rows)
 
 Every per-pixel step runs in HIP (evalpath.hip): the flips and 0.75/1.25
@@ -19,8 +22,18 @@ Lab -> RGB, filter2D sharpening x0.15, /255.  cv2 is absent, so those kernels
 follow OpenCV's documented algorithms (parity unpinned, oracle/imgproc_ref.py).
 preprocess=None skips the step, a callable replaces it.
 
-Not built: instance splitting / COCO metrics (cv2, skimage,
-pycocotools).
+The instance split runs in HIP as well (instances.hip): the 2x2 opening, the
+erosion ladder, 8-connected labelling (skimage.measure.label's numbering) and
+Suzuki-Abe outer-border following for the compactness score; the host keeps
+only the reference's control flow over per-region pixel counts.  As with the
+image preprocessing, cv2 is absent: which contour cv2.findContours lists first
+for an instance of several components (taken as the one discovered last) and
+cv2.arcLength's float32 segment rounding (the perimeter here is the exact
+n_axis + n_diag * sqrt(2) in float64) are unpinned; both live in
+ops.outer_perimeter / _perimeter alone.
+
+Not built: COCO mAP (pycocotools) -- evaluate() returns no
+bbox_mAP / segm_mAP keys.
 """
 from __future__ import annotations
 
@@ -32,9 +45,31 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .metrics import calculate_semantic_metrics
+from .metrics import calculate_instance_metrics, calculate_semantic_metrics, calculate_viability_metrics
 
 TTA_SCALES = (0.75, 1.25)
+
+# semantic_to_instances (train_eval.py:686, 793-798, 842)
+LARGE_REGION = 200
+MAX_AREA = 1500
+MIN_AREA_CLASS = {1: 3, 2: 5}
+MAX_INSTANCES = 500
+
+# the rows evaluate() averages (train_eval.py:854-880) without bbox_mAP / segm_mAP
+EVALUATE_KEYS = ("sem_mean_iou", "sem_mean_dice", "sem_background_iou", "sem_background_dice", "sem_live_iou",
+                 "sem_live_dice", "sem_dead_iou", "sem_dead_dice", "live_iou", "live_precision", "live_recall",
+                 "live_ap", "dead_iou", "dead_precision", "dead_recall", "dead_ap", "viability_accuracy",
+                 "pred_viability", "gt_viability", "pred_live_count", "pred_dead_count", "gt_live_count",
+                 "gt_dead_count")
+
+
+def _perimeter(n_axis: int, n_diag: int) -> float:
+    """cv2.arcLength(contours[0], True) of the followed border: axis steps + diagonal steps * sqrt(2)."""
+    return n_axis + n_diag * math.sqrt(2.0)
+
+
+def _count(c: torch.Tensor) -> int:
+    return int(c.item())
 
 
 def reference_preprocess(image: torch.Tensor) -> torch.Tensor:
@@ -132,3 +167,132 @@ class Evaluator:
                 for k, v in calculate_semantic_metrics(pred, item["semantic_mask"]).items():
                     acc.setdefault(k, []).append(v)
         return {k: float(np.mean(v)) for k, v in acc.items()}
+
+    # ---- train_eval.py:654-850 -------------------------------------------------
+    def _split_large_region(self, region, area: int, final, next_label: int, min_area: int) -> int:
+        """The erosion ladder of one region of >= 200 px (train_eval.py:697-785): writes the pieces into
+        final (later writes overwrite earlier ones, in stream order) and returns the next free label."""
+        def emit(mask, count):
+            nonlocal next_label
+            if count >= min_area:
+                ops.write_label(mask, next_label, final)
+                next_label += 1
+
+        def pieces(eroded_labels, n, ksize, iterations, within):
+            for sub in range(1, n + 1):
+                sub_region, _ = ops.mask_eq(eroded_labels, sub)
+                dil, cnt = ops.mask_and(ops.morph_u8(sub_region, ksize, True, iterations), within)
+                yield dil, _count(cnt)
+
+        it = max(2, min(area // 1000, 8))
+        sub_markers, sub_num, _ = ops.label_components(ops.morph_u8(region, 3, False, it))
+        if sub_num > 1:
+            for dilated, cnt in pieces(sub_markers, sub_num, 3, it, region):
+                if cnt > LARGE_REGION:
+                    m2, n2, _ = ops.label_components(ops.morph_u8(dilated, 3, False, 2))
+                    if n2 > 1:
+                        for d2, c2 in pieces(m2, n2, 3, 2, dilated):
+                            emit(d2, c2)
+                    else:
+                        emit(dilated, cnt)
+                else:
+                    emit(dilated, cnt)
+            return next_label
+        eroded = region
+        for _ in range(3):
+            eroded = ops.morph_u8(eroded, 3, False, 1)
+            m, n, _ = ops.label_components(eroded)
+            if n > 1:
+                for d, c in pieces(m, n, 3, 3, region):
+                    emit(d, c)
+                return next_label
+        m2, n2, _ = ops.label_components(ops.morph_u8(region, 5, False, 3))
+        if n2 > 1:
+            for d2, c2 in pieces(m2, n2, 5, 3, region):
+                emit(d2, c2)
+        else:
+            emit(region, area)
+        return next_label
+
+    def semantic_to_instances(self, semantic_mask, min_area: int = 3) -> tuple:
+        """Semantic mask [h, w] (numpy or tensor; 1 live, 2 dead) -> (instance_masks, instance_labels,
+        instance_scores) as the reference returns them; the masks are [h, w] uint8 device tensors (the
+        form CellDataset hands out ground truth in), labels 0 live / 1 dead, scores float64."""
+        sem = semantic_mask if isinstance(semantic_mask, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(semantic_mask))
+        if sem.dtype not in (torch.int32, torch.int64):
+            sem = sem.long()
+        dev = sem.device if sem.is_cuda else (self.device if str(self.device) != "cpu" else "cuda")
+        sem = sem.to(dev).contiguous()
+        instance_masks, instance_labels, instance_scores = [], [], []
+        for class_id in (1, 2):
+            class_mask, cnt = ops.mask_eq(sem, class_id)
+            if _count(cnt) == 0:
+                continue
+            class_mask = ops.morph_u8(ops.morph_u8(class_mask, 2, False), 2, True)  # MORPH_OPEN, 2x2
+            markers, num_labels, areas = ops.label_components(class_mask)
+            final = torch.zeros_like(markers)
+            next_label = 1
+            if num_labels:
+                areas = areas.cpu().numpy()
+                table = np.zeros(num_labels, np.int32)
+                for label_id in range(1, num_labels + 1):
+                    area = int(areas[label_id - 1])
+                    if area < LARGE_REGION:
+                        table[label_id - 1] = next_label
+                        next_label += 1
+                    else:
+                        region, _ = ops.mask_eq(markers, label_id)
+                        next_label = self._split_large_region(region, area, final, next_label, min_area)
+                if table.any():  # every small region in one pass; regions are disjoint components
+                    ops.relabel_table(markers, ops.upload(table, dev), final)
+            num_final = next_label - 1
+            if num_final:
+                stats = ops.outer_perimeter(final, num_final).cpu().numpy()
+                lo, hi = max(MIN_AREA_CLASS[class_id], min_area), MAX_AREA
+                slots = np.full(num_final, -1, np.int32)
+                scores = []
+                for k in range(num_final):
+                    n_axis, n_diag, area = (int(v) for v in stats[k, :3])
+                    if area < lo or area > hi:
+                        continue
+                    perimeter = _perimeter(n_axis, n_diag)
+                    compactness = 4 * np.pi * area / (perimeter ** 2) if perimeter > 0 else 0.5
+                    slots[k] = len(scores)
+                    scores.append(0.7 * min(area / 150.0, 1.0) + 0.3 * compactness)
+                if scores:
+                    planes = ops.expand_labels(final, ops.upload(slots, dev), len(scores))
+                    instance_masks += list(planes)
+                    instance_labels += [class_id - 1] * len(scores)
+                    instance_scores += scores
+            if len(instance_masks) > MAX_INSTANCES:  # inside the class loop, on the combined list (:842-848)
+                keep = sorted(range(len(instance_scores)), key=lambda i: instance_scores[i],
+                              reverse=True)[:MAX_INSTANCES]
+                instance_masks = [instance_masks[i] for i in keep]
+                instance_labels = [instance_labels[i] for i in keep]
+                instance_scores = [instance_scores[i] for i in keep]
+        return instance_masks, instance_labels, instance_scores
+
+    # ---- train_eval.py:852-1021 ------------------------------------------------
+    def evaluate(self, dataloader) -> Dict[str, float]:
+        """Mean over the images of the semantic, instance and viability rows, with the reference's keys
+        (a key that collected nothing gives 0.0).  bbox_mAP and segm_mAP need pycocotools and are left out
+        of the dict: a silent zero would read as a measurement."""
+        acc: Dict[str, list] = {k: [] for k in EVALUATE_KEYS}
+
+        def collect(metrics):
+            for k, v in metrics.items():
+                if k in acc:
+                    acc[k].append(v)
+
+        for batch in dataloader:
+            for i, item in enumerate(batch["batch_items"]):
+                gt_masks, gt_labels = item["instance_masks"], item["instance_labels"]
+                pred = self.predict_semantic_mask(batch["images"][i])
+                collect(calculate_semantic_metrics(pred, item["semantic_mask"]))
+                masks, labels, scores = self.semantic_to_instances(pred)
+                collect(calculate_instance_metrics(masks, labels, scores, gt_masks, gt_labels))
+                collect(calculate_viability_metrics(sum(1 for l in labels if l == 0), sum(1 for l in labels if l == 1),
+                                                    sum(1 for l in gt_labels if l == 0),
+                                                    sum(1 for l in gt_labels if l == 1)))
+        return {k: (np.mean(v) if v else 0.0) for k, v in acc.items()}

@@ -566,6 +566,118 @@ def probs_to_mask(probs):
     return mask
 
 
+# ---- instance-level evaluation (instances.hip) -----------------------------------------
+MORPH_ELEMS = {2: 0, 3: 1, 5: 2}  # side of cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)) -> eunet_morph_u8 elem
+
+
+def _u8(t):
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dtype != torch.uint8:
+        raise _lib.EunetError(f"instance ops take uint8 masks, got {t.dtype}")
+    return t.contiguous()
+
+
+def pack_masks(masks):
+    """masks uint8 [n, h, w] (non-zero = set) -> (packed int64 [n, ceil(hw/64)] holding the 64-bit words,
+    areas int64 [n])."""
+    masks = _u8(masks)
+    n, h, w = masks.shape
+    words = (h * w + 63) // 64
+    packed = torch.empty(n, words, dtype=torch.int64, device=masks.device)
+    areas = torch.empty(n, dtype=torch.int64, device=masks.device)
+    call("eunet_pack_masks", _ptr(masks), n, h, w, _ptr(packed), _ptr(areas), _stream())
+    return packed, areas
+
+
+def pairwise_overlap(pa, pb):
+    """packed [P, words] x packed [G, words] -> inter int64 [P, G] = |a & b| per pair."""
+    if pa.shape[1] != pb.shape[1]:
+        raise ValueError(f"packed widths differ: {pa.shape[1]} vs {pb.shape[1]}")
+    inter = torch.empty(pa.shape[0], pb.shape[0], dtype=torch.int64, device=pa.device)
+    call("eunet_pairwise_overlap", _ptr(pa.contiguous()), pa.shape[0], _ptr(pb.contiguous()), pb.shape[0],
+         pa.shape[1], _ptr(inter), _stream())
+    return inter
+
+
+def morph_u8(img, ksize: int, dilate: bool, iterations: int = 1):
+    """cv2.erode / cv2.dilate of a uint8 [h, w] image by the MORPH_ELLIPSE element of side ksize (2, 3, 5)."""
+    img = _u8(img)
+    h, w = img.shape
+    out = torch.empty_like(img)
+    tmp = torch.empty_like(img) if iterations > 1 else None
+    call("eunet_morph_u8", _ptr(img), _ptr(out), _ptr(tmp), h, w, MORPH_ELEMS[ksize], int(dilate), int(iterations),
+         _stream())
+    return out
+
+
+def label_components(img):
+    """8-connected components of a uint8 [h, w] image -> (labels int32 [h, w], n, areas int32 [n] on the device);
+    numbered 1..n in raster order of each component's first pixel.  Synchronises to read n."""
+    img = _u8(img)
+    h, w = img.shape
+    nbytes = c_size_t()
+    call("eunet_label_workspace_bytes", h, w, ctypes.byref(nbytes))
+    cap = ((h + 1) // 2) * ((w + 1) // 2)
+    labels = torch.empty(h, w, dtype=torch.int32, device=img.device)
+    ws = torch.empty(nbytes.value // 4, dtype=torch.int32, device=img.device)
+    areas = torch.empty(cap + 1, dtype=torch.int32, device=img.device)  # [cap] holds n
+    call("eunet_label_components", _ptr(img), h, w, _ptr(labels), _ptr(areas[cap:]), _ptr(areas), cap, _ptr(ws),
+         _stream())
+    n = int(areas[cap].item())
+    return labels, n, areas[:n]
+
+
+def outer_perimeter(labels, n: int):
+    """Per label 1..n of an int32 [h, w] label map: stats int32 [n, 8] = (axis steps, diagonal steps, area,
+    start pixel, x0, y0, x1, y1) of the outer border of the label's chosen component."""
+    if labels.dtype != torch.int32:
+        raise _lib.EunetError("outer_perimeter: int32 label map")
+    labels = labels.contiguous()
+    h, w = labels.shape
+    stats = torch.empty(n, 8, dtype=torch.int32, device=labels.device)
+    ws = torch.empty(h * w, dtype=torch.int32, device=labels.device)
+    call("eunet_outer_perimeter", _ptr(labels), h, w, n, _ptr(stats), _ptr(ws), _stream())
+    return stats
+
+
+def mask_eq(src, value: int):
+    """(src == value) as uint8 0/1 of an int32 / int64 tensor, and the device int64 [1] count of ones."""
+    if src.dtype not in (torch.int32, torch.int64):
+        raise _lib.EunetError(f"mask_eq: int32 or int64 source, got {src.dtype}")
+    src = src.contiguous()
+    dst = torch.empty(src.shape, dtype=torch.uint8, device=src.device)
+    count = torch.empty(1, dtype=torch.int64, device=src.device)
+    call("eunet_mask_eq", _ptr(src), src.element_size(), src.numel(), int(value), _ptr(dst), _ptr(count), _stream())
+    return dst, count
+
+
+def mask_and(a, b):
+    """(a != 0) & (b != 0) as uint8 0/1, and the device int64 [1] count of ones."""
+    a, b = _u8(a), _u8(b)
+    dst = torch.empty_like(a)
+    count = torch.empty(1, dtype=torch.int64, device=a.device)
+    call("eunet_mask_and", _ptr(a), _ptr(b), a.numel(), _ptr(dst), _ptr(count), _stream())
+    return dst, count
+
+
+def write_label(mask, label: int, markers):
+    """markers[mask != 0] = label, in place (int32 markers)."""
+    call("eunet_write_label", _ptr(_u8(mask)), markers.numel(), int(label), _ptr(markers), _stream())
+
+
+def relabel_table(labels, table, markers):
+    """markers[i] = table[labels[i] - 1] where that entry is > 0, in place (int32 everywhere)."""
+    call("eunet_relabel_table", _ptr(labels), labels.numel(), _ptr(table), table.numel(), _ptr(markers), _stream())
+
+
+def expand_labels(labels, table, m: int):
+    """uint8 [m, h, w]: plane table[l - 1] is the mask of label l (entries < 0 are dropped)."""
+    out = torch.empty(m, *labels.shape, dtype=torch.uint8, device=labels.device)
+    call("eunet_expand_labels", _ptr(labels), labels.numel(), _ptr(table), table.numel(), m, _ptr(out), _stream())
+    return out
+
+
 # ---- dual-branch fusion (fusion.hip) -------------------------------------------------
 def fusion_tiles(n, h, w):
     t, gt = c_int(), c_int()

@@ -266,7 +266,7 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
  * eunet_debug_enabled: 1 in the debug build, 0 in the release library (where the checks compile away).
  * eunet_debug_status: synchronises the device; *count = failed checks since the last reset,
  * *unit_line = unit * 100000 + source line of the first (units: 1 capi, 2 conv3x3, 3 bn_pool_up,
- * 4 head; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
+ * 4 head, 5 instances; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
 int eunet_debug_enabled(void);
 int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset);
 int eunet_debug_selftest(void* stream);
@@ -377,6 +377,61 @@ int eunet_accumulate(float* acc, const float* p, long long n, int mode, float co
  * zero dead-cell probability) -> mask int64 [h][w]; counts: 2 int64 of workspace. */
 int eunet_probs_to_mask(const float* probs, int k, int h, int w, int64_t* mask,
                         int64_t* counts, void* stream);
+
+/* ---- instance-level evaluation (instances.hip) ------------------------------
+ * Pairwise mask overlap (metrics.py:61-194, calculate_instance_metrics: the calculate_iou
+ * of metrics.py:12-18 per (prediction, ground-truth) pair).  eunet_pack_masks: masks
+ * uint8 [n][h][w] (non-zero = set) -> packed uint64 [n][ceil(hw/64)], bit b of word j =
+ * pixel 64 j + b, the tail word zero-filled; areas int64 [n] = set pixels per mask.
+ * h * w < 2^31. */
+int eunet_pack_masks(const uint8_t* masks, int n, int h, int w, uint64_t* packed, int64_t* areas,
+                     void* stream);
+/* inter int64 [p][g] = sum over words of popcount(a[p][.] & b[g][.]) (np.logical_and(m1,
+ * m2).sum(), metrics.py:14), zeroed by the call.  IoU = inter / (area_p + area_g - inter)
+ * is formed on the host.  Masks may overlap one another. */
+int eunet_pairwise_overlap(const uint64_t* a, int p, const uint64_t* b, int g, long long words,
+                           int64_t* inter, void* stream);
+/* cv2.erode / cv2.dilate / cv2.morphologyEx(MORPH_OPEN) (train_eval.py:674, 702, 712, 719,
+ * 725, 749, 756, 768, 775) of a uint8 [h][w] image by the element cv2.getStructuringElement(
+ * cv2.MORPH_ELLIPSE, (k, k)) returns (train_eval.py:673, 699, 767): elem 0 -> k = 2,
+ * 1 -> k = 3, 2 -> k = 5.  OpenCV conventions: un-reflected element, anchor (k/2, k/2),
+ * pixels outside the image neither erode nor dilate.  iterations > 1 ping-pong through tmp
+ * ([h][w], may be null for one iteration); src, dst, tmp distinct. */
+int eunet_morph_u8(const uint8_t* src, uint8_t* dst, uint8_t* tmp, int h, int w, int elem,
+                   int dilate, int iterations, void* stream);
+/* skimage.measure.label(img, connectivity=2, return_num=True) (train_eval.py:678, 705, 720,
+ * 750, 769) of a uint8 [h][w] image (non-zero = set): labels int32 [h][w], numbered 1..n in
+ * raster order of each component's first pixel; *n_out (device int32) = n; areas int32
+ * [areas_cap >= ceil(h/2) * ceil(w/2)] = pixels per label, zeroed by the call.
+ * ws: eunet_label_workspace_bytes of device workspace. */
+int eunet_label_workspace_bytes(int h, int w, size_t* bytes);
+int eunet_label_components(const uint8_t* img, int h, int w, int32_t* labels, int32_t* n_out,
+                           int32_t* areas, int areas_cap, int32_t* ws, void* stream);
+/* cv2.findContours(mask, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)[0][0] + cv2.arcLength(., True)
+ * (train_eval.py:819-821) for every label k = 1..n of an int32 label map at once (Suzuki-Abe
+ * outer-border following, 8-connectivity): stats int32 [n][8] = (axis-aligned chain steps,
+ * diagonal chain steps, area, start pixel, bounding box x0, y0, x1, y1); the perimeter is
+ * n_axis + n_diag * sqrt(2) on the host.  A label with several components is followed on the
+ * one whose raster-first pixel comes last (OpenCV lists contours in reverse order of
+ * discovery).  ws: int32 [h * w] of device workspace. */
+int eunet_outer_perimeter(const int32_t* labels, int h, int w, int n, int32_t* stats, int32_t* ws,
+                          void* stream);
+/* Per-pixel helpers of semantic_to_instances (train_eval.py:654-850), n elements each:
+ * mask_eq: dst = (src == value) as 0/1 for an int32 / int64 source (elem_bytes 4 / 8; :666,
+ * :689, :710), count (device int64) = ones; mask_and: cv2.bitwise_and of two 0/1 images + its
+ * sum (:713-716); write_label: markers[mask != 0] = label (:694, :729 ...); relabel_table:
+ * markers[i] = table[labels[i] - 1] where that entry is > 0 (every region under 200 px in
+ * one pass, :692-695); expand_labels: out uint8 [m][n], out[table[labels[i] - 1]][i] = 1
+ * where the entry is >= 0 (instance_mask = final_markers == label_id, :805), zeroed first. */
+int eunet_mask_eq(const void* src, int elem_bytes, long long n, long long value, uint8_t* dst,
+                  int64_t* count, void* stream);
+int eunet_mask_and(const uint8_t* a, const uint8_t* b, long long n, uint8_t* dst, int64_t* count,
+                   void* stream);
+int eunet_write_label(const uint8_t* mask, long long n, int label, int32_t* markers, void* stream);
+int eunet_relabel_table(const int32_t* labels, long long n, const int32_t* table, int n_labels,
+                        int32_t* markers, void* stream);
+int eunet_expand_labels(const int32_t* labels, long long n, const int32_t* table, int n_labels,
+                        int m, uint8_t* out, void* stream);
 
 /* ---- dual-branch fusion (fusion.hip) -----------------------------------------
  * SMP-path EnhancedUNet (models.py:253-302, 316-333): ff = cat(unetpp, deeplab) with the
