@@ -41,6 +41,150 @@ __global__ __launch_bounds__(NT) void pack_masks_kernel(const uint8_t* masks, lo
   if (lane == 0 && area) atomicAdd(areas + n, (unsigned long long)area);
 }
 
+// ---- the same pass with the bounding box of the set pixels (cv2.boundingRect, train_eval.py:959, 978):
+// bbox[n] = (xmin, ymin, xmax, ymax), inclusive, preset to (w, h, -1, -1) by bbox_init_kernel.  A 64-pixel
+// word crosses image rows whenever w % 64 != 0, so x and y are derived per lane; min / max are reduced in
+// the wave (shuffles), in the block (LDS), then by integer atomicMin / atomicMax (order-free).
+__global__ __launch_bounds__(NT) void bbox_init_kernel(int* bbox, int n, int h, int w) {
+  const int k = blockIdx.x * NT + threadIdx.x;
+  if (k >= n) return;
+  bbox[4 * k + 0] = w; bbox[4 * k + 1] = h; bbox[4 * k + 2] = -1; bbox[4 * k + 3] = -1;
+}
+
+__global__ __launch_bounds__(NT) void pack_masks_bbox_kernel(const uint8_t* masks, long long hw, int h, int w,
+                                                             long long words, unsigned long long* packed,
+                                                             unsigned long long* areas, int* bbox) {
+  __shared__ int red[NT / 64][4];
+  const int n = blockIdx.y;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint8_t* m = masks + (long long)n * hw;
+  unsigned long long* out = packed + (long long)n * words;
+  unsigned int area = 0;  // hw < 2^31
+  int xmin = w, ymin = h, xmax = -1, ymax = -1;
+  for (long long j = (long long)blockIdx.x * (NT / 64) + wv; j < words; j += (long long)gridDim.x * (NT / 64)) {
+    const long long px = j * 64 + lane;
+    const bool set = px < hw && m[px] != 0;
+    const unsigned long long word = __ballot(set);
+    if (set) {
+      const int y = (int)((unsigned)px / (unsigned)w), x = (int)((unsigned)px - (unsigned)y * (unsigned)w);
+      EUNET_DASSERT(x >= 0 && x < w && y >= 0 && y < h);
+      xmin = min(xmin, x); ymin = min(ymin, y);
+      xmax = max(xmax, x); ymax = max(ymax, y);
+    }
+    if (lane == 0) {
+      EUNET_DASSERT(j >= 0 && j < words);
+      out[j] = word;
+      area += (unsigned)__popcll(word);
+    }
+  }
+  if (lane == 0 && area) atomicAdd(areas + n, (unsigned long long)area);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    xmin = min(xmin, __shfl_xor(xmin, o, 64)); ymin = min(ymin, __shfl_xor(ymin, o, 64));
+    xmax = max(xmax, __shfl_xor(xmax, o, 64)); ymax = max(ymax, __shfl_xor(ymax, o, 64));
+  }
+  if (lane == 0) {
+    red[wv][0] = xmin; red[wv][1] = ymin; red[wv][2] = xmax; red[wv][3] = ymax;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 1; i < NT / 64; ++i) {
+      xmin = min(xmin, red[i][0]); ymin = min(ymin, red[i][1]);
+      xmax = max(xmax, red[i][2]); ymax = max(ymax, red[i][3]);
+    }
+    if (xmax >= 0) {  // this block saw a set pixel
+      int* b = bbox + 4ll * n;
+      atomicMin(b + 0, xmin); atomicMin(b + 1, ymin);
+      atomicMax(b + 2, xmax); atomicMax(b + 3, ymax);
+    }
+  }
+}
+
+// ---- COCOeval.evaluateImg's greedy matching of one image (pycocotools cocoeval.py), every class, both IoU
+// types and every threshold in one launch: one block per (class, threshold, type).  The block walks its
+// class's detections in the order given (the host sorted them); for each, the lanes stride over the ground
+// truths of the class and reduce to the untaken one with the largest IoU >= min(thr, 1 - 1e-10), the LARGER
+// index on equal IoU (pycocotools skips on `<`, so a later equal ground truth overwrites an earlier one).
+// Taken flags live in an LDS bitset.  IoU is int / int in fp64 (a correctly rounded divide: bit-equal to
+// the host's).  Every loop is bounded by D or G; blocks are independent of one another.
+constexpr int CM_MAX_D = 4096, CM_MAX_G = 8192, CM_MAX_T = 16;
+struct CocoThrs {
+  double v[CM_MAX_T];
+};
+
+__device__ __forceinline__ double coco_bbox_iou(int4 a, int4 b) {  // (x, y, w, h)
+  const int iw = min(a.x + a.z, b.x + b.z) - max(a.x, b.x);
+  const int ih = min(a.y + a.w, b.y + b.w) - max(a.y, b.y);
+  if (iw <= 0 || ih <= 0) return 0.0;
+  const long long i = (long long)iw * ih;
+  const long long u = (long long)a.z * a.w + (long long)b.z * b.w - i;
+  return (double)i / (double)u;
+}
+
+__global__ __launch_bounds__(NT) void coco_match_kernel(const long long* inter, const long long* area_d,
+                                                        const long long* area_g, const int4* box_d,
+                                                        const int4* box_g, const int* cls_d, const int* cls_g, int D,
+                                                        int G, CocoThrs thrs, int T, int* match) {
+  __shared__ unsigned taken[CM_MAX_G / 32];
+  __shared__ double w_iou[NT / 64];
+  __shared__ int w_g[NT / 64];
+  const int c = blockIdx.x, t = blockIdx.y, type = blockIdx.z;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < CM_MAX_G / 32; i += NT) taken[i] = 0u;
+  __syncthreads();
+  const double thr = fmin(thrs.v[t], 1.0 - 1e-10);
+  int* out = match + ((long long)type * T + t) * D;
+  for (int d = 0; d < D; ++d) {
+    if (cls_d[d] != c) continue;  // block-uniform
+    const long long* row = inter + (long long)d * G;
+    const long long ad = area_d[d];
+    const int4 bd = box_d[d];
+    double best = -1.0;
+    int bg = -1;
+    for (int g = threadIdx.x; g < G; g += NT) {
+      if (cls_g[g] != c || ((taken[g >> 5] >> (g & 31)) & 1u)) continue;
+      double iou;
+      if (type == 0) {
+        iou = coco_bbox_iou(bd, box_g[g]);
+      } else {
+        const long long it = row[g];
+        iou = it == 0 ? 0.0 : (double)it / (double)(ad + area_g[g] - it);
+      }
+      if (iou >= thr && iou >= best) {  // g grows within a lane: >= keeps the later of equals
+        best = iou;
+        bg = g;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double oi = __shfl_xor(best, o, 64);
+      const int og = __shfl_xor(bg, o, 64);
+      if (oi > best || (oi == best && og > bg)) {
+        best = oi;
+        bg = og;
+      }
+    }
+    if (lane == 0) {
+      w_iou[wv] = best;
+      w_g[wv] = bg;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int i = 1; i < NT / 64; ++i)
+        if (w_iou[i] > best || (w_iou[i] == best && w_g[i] > bg)) {
+          best = w_iou[i];
+          bg = w_g[i];
+        }
+      EUNET_DASSERT(bg >= -1 && bg < G);
+      if (bg >= 0) taken[bg >> 5] |= 1u << (bg & 31);
+      out[d] = bg;
+    }
+    __syncthreads();
+  }
+}
+
 // ---- pairwise overlap: inter[p][g] += sum over words of popcount(a[p][k] & b[g][k]); a small "GEMM".
 // A block owns a 64 x 64 tile of pairs and one slice of the word dimension (blockIdx.z); it stages KC words
 // of 64 + 64 rows in LDS (k-major, so a wave reads consecutive rows) and each lane keeps a 4 x 4 register
@@ -479,6 +623,53 @@ int eunet_pack_masks(const uint8_t* masks, int n, int h, int w, uint64_t* packed
   pack_masks_kernel<<<dim3((unsigned)bx, n), NT, 0, s>>>(masks, hw, words, (unsigned long long*)packed,
                                                           (unsigned long long*)areas);
   EUNET_LAUNCH_CHECK("pack_masks");
+  return EUNET_OK;
+}
+
+int eunet_pack_masks_bbox(const uint8_t* masks, int n, int h, int w, uint64_t* packed, int64_t* areas, int32_t* bbox,
+                          void* stream) {
+  EUNET_REQUIRE(masks && packed && areas && bbox && n > 0 && h > 0 && w > 0, "pack_masks_bbox: bad args");
+  const long long hw = (long long)h * w;
+  EUNET_REQUIRE(hw < (1ll << 31), "pack_masks_bbox: h * w must be below 2^31");
+  EUNET_REQUIRE(n <= 65535, "pack_masks_bbox: at most 65535 masks per call");
+  hipStream_t s = (hipStream_t)stream;
+  if (!zero_async(areas, sizeof(int64_t) * n, s, "pack_masks_bbox")) return EUNET_ERR_HIP;
+  bbox_init_kernel<<<cdiv(n, NT), NT, 0, s>>>(bbox, n, h, w);
+  const long long words = (hw + 63) / 64;
+  long long bx = (words + NT / 64 - 1) / (NT / 64);
+  if (bx > 512) bx = 512;
+  pack_masks_bbox_kernel<<<dim3((unsigned)bx, n), NT, 0, s>>>(masks, hw, h, w, words, (unsigned long long*)packed,
+                                                               (unsigned long long*)areas, bbox);
+  EUNET_LAUNCH_CHECK("pack_masks_bbox");
+  return EUNET_OK;
+}
+
+int eunet_coco_match(const int64_t* inter, const int64_t* area_d, const int64_t* area_g, const int32_t* box_d,
+                     const int32_t* box_g, const int32_t* cls_d, const int32_t* cls_g, int d, int g,
+                     const double* thrs, int t, int32_t* match, void* stream) {
+  EUNET_REQUIRE(inter && area_d && area_g && box_d && box_g && cls_d && cls_g && thrs && match && d > 0 && g > 0 &&
+                    t > 0,
+                "coco_match: bad args");
+  EUNET_REQUIRE(d <= CM_MAX_D, "coco_match: at most %d detections per image (got %d)", CM_MAX_D, d);
+  EUNET_REQUIRE(g <= CM_MAX_G, "coco_match: at most %d ground truths per image (got %d)", CM_MAX_G, g);
+  EUNET_REQUIRE(t <= CM_MAX_T, "coco_match: at most %d IoU thresholds (got %d)", CM_MAX_T, t);
+  EUNET_REQUIRE((((uintptr_t)box_d | (uintptr_t)box_g) & 15) == 0, "coco_match: boxes must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  // the classes select the block that writes a detection's row: read them back and check them here
+  std::vector<int32_t> cls((size_t)d + g);
+  if (hipMemcpyAsync(cls.data(), cls_d, sizeof(int32_t) * d, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(cls.data() + d, cls_g, sizeof(int32_t) * g, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    eunet::set_error("coco_match: reading the classes back failed");
+    return EUNET_ERR_HIP;
+  }
+  for (int32_t c : cls) EUNET_REQUIRE(c == 0 || c == 1, "coco_match: classes must be 0 or 1 (got %d)", (int)c);
+  CocoThrs th = {};
+  for (int i = 0; i < t; ++i) th.v[i] = thrs[i];
+  coco_match_kernel<<<dim3(2, t, 2), NT, 0, s>>>((const long long*)inter, (const long long*)area_d,
+                                                 (const long long*)area_g, (const int4*)box_d, (const int4*)box_g,
+                                                 cls_d, cls_g, d, g, th, t, match);
+  EUNET_LAUNCH_CHECK("coco_match");
   return EUNET_OK;
 }
 

@@ -112,6 +112,8 @@ SIGNATURES = {
     "eunet_accumulate": [_f, _f, c_int64, c_int, c_float, c_void_p],
     "eunet_probs_to_mask": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
     "eunet_pack_masks": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
+    "eunet_pack_masks_bbox": [_f, c_int, c_int, c_int, _f, _f, _f, c_void_p],
+    "eunet_coco_match": [_f, _f, _f, _f, _f, _f, _f, c_int, c_int, POINTER(ctypes.c_double), c_int, _f, c_void_p],
     "eunet_pairwise_overlap": [_f, c_int, _f, c_int, c_int64, _f, c_void_p],
     "eunet_morph_u8": [_f, _f, _f, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "eunet_label_workspace_bytes": [c_int, c_int, POINTER(c_size_t)],

@@ -7,7 +7,8 @@
     .predict_semantic_mask(image) -> int64 mask [h,w] (numpy)   # train_eval.py:570-606
     .semantic_to_instances(mask, min_area=3)                    # train_eval.py:654-850
         -> (instance_masks, instance_labels, instance_scores)
-    .evaluate(dataloader) -> mean semantic / instance / viability rows   # train_eval.py:852-1021
+    .evaluate(dataloader, coco_map=False) -> mean semantic / instance / viability rows   # train_eval.py:852-1021
+        (coco_map=True adds bbox_mAP / segm_mAP, train_eval.py:951-992, 1007-1011)
     .evaluate_semantic(dataloader) -> mean semantic metrics     # train_eval.py:852-904 (semantic rows)
 
 Every per-pixel step runs in HIP (evalpath.hip): the flips and 0.75/1.25
@@ -32,12 +33,18 @@ cv2.arcLength's float32 segment rounding (the perimeter here is the exact
 n_axis + n_diag * sqrt(2) in float64) are unpinned; both live in
 ops.outer_perimeter / _perimeter alone.
 
-Not built: COCO mAP (pycocotools) -- evaluate() returns no
-bbox_mAP / segm_mAP keys.
+COCO mAP (bbox_mAP / segm_mAP, COCOeval stats[0]) is built natively, without
+pycocotools: evaluate(coco_map=True) packs each image's masks with their
+bounding boxes, forms the pairwise overlap and runs COCOeval's greedy matching
+on the device (eunet_pack_masks_bbox, eunet_pairwise_overlap,
+eunet_coco_match); only the match tables come back, and
+metrics.coco_map_from_matches accumulates them once at the end.  The default
+evaluate() returns the 23 EVALUATE_KEYS rows as before.
 """
 from __future__ import annotations
 
 import math
+import warnings
 from typing import Callable, Dict, Optional, Union
 
 import numpy as np
@@ -45,7 +52,8 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .metrics import calculate_instance_metrics, calculate_semantic_metrics, calculate_viability_metrics
+from .metrics import (calculate_instance_metrics, calculate_semantic_metrics, calculate_viability_metrics,
+                      coco_image_matches, coco_map_from_matches)
 
 TTA_SCALES = (0.75, 1.25)
 
@@ -61,6 +69,8 @@ EVALUATE_KEYS = ("sem_mean_iou", "sem_mean_dice", "sem_background_iou", "sem_bac
                  "live_ap", "dead_iou", "dead_precision", "dead_recall", "dead_ap", "viability_accuracy",
                  "pred_viability", "gt_viability", "pred_live_count", "pred_dead_count", "gt_live_count",
                  "gt_dead_count")
+# the two rows evaluate(coco_map=True) adds (train_eval.py:871-872, 1007-1011)
+COCO_KEYS = ("bbox_mAP", "segm_mAP")
 
 
 def _perimeter(n_axis: int, n_diag: int) -> float:
@@ -274,11 +284,16 @@ class Evaluator:
         return instance_masks, instance_labels, instance_scores
 
     # ---- train_eval.py:852-1021 ------------------------------------------------
-    def evaluate(self, dataloader) -> Dict[str, float]:
+    def evaluate(self, dataloader, coco_map: bool = False) -> Dict[str, float]:
         """Mean over the images of the semantic, instance and viability rows, with the reference's keys
-        (a key that collected nothing gives 0.0).  bbox_mAP and segm_mAP need pycocotools and are left out
-        of the dict: a silent zero would read as a measurement."""
+        (a key that collected nothing gives 0.0).  coco_map=True adds COCO_KEYS (bbox_mAP, segm_mAP:
+        COCOeval stats[0] over all images, metrics.calculate_coco_metrics' value): per image the matching
+        runs on the device and only scores, match tables and ground-truth counts are kept, accumulated once
+        at the end.  Without the flag those keys are left out of the dict."""
         acc: Dict[str, list] = {k: [] for k in EVALUATE_KEYS}
+        coco_bbox, coco_segm = [], []
+        n_pred = n_gt = 0  # over all images; ground-truth ids are the running positions (metrics.py:240-242)
+        orphan = False  # predictions on an image without ground truth: COCO.loadRes refuses them
 
         def collect(metrics):
             for k, v in metrics.items():
@@ -295,4 +310,23 @@ class Evaluator:
                 collect(calculate_viability_metrics(sum(1 for l in labels if l == 0), sum(1 for l in labels if l == 1),
                                                     sum(1 for l in gt_labels if l == 0),
                                                     sum(1 for l in gt_labels if l == 1)))
-        return {k: (np.mean(v) if v else 0.0) for k, v in acc.items()}
+                if coco_map:  # the image id is the running counter of train_eval.py:898: one entry per image
+                    if len(gt_labels) == 0:
+                        orphan = orphan or len(labels) > 0
+                    else:
+                        eb, es = coco_image_matches(masks, labels, scores, gt_masks, gt_labels,
+                                                    range(n_gt, n_gt + len(gt_labels)))
+                        coco_bbox.append(eb)
+                        coco_segm.append(es)
+                    n_pred += len(labels)
+                    n_gt += len(gt_labels)
+        result = {k: (np.mean(v) if v else 0.0) for k, v in acc.items()}
+        if coco_map:
+            result.update({k: 0.0 for k in COCO_KEYS})
+            if orphan and n_gt:
+                warnings.warn("evaluate: predictions on an image without ground truth; the reference's "
+                              "COCO.loadRes refuses such results, so bbox_mAP and segm_mAP are 0.0")
+            elif n_pred and n_gt:
+                result["bbox_mAP"] = coco_map_from_matches(coco_bbox)
+                result["segm_mAP"] = coco_map_from_matches(coco_segm)
+        return result

@@ -14,11 +14,22 @@ on the host exactly as the reference forms them (int / int in float64), and so
 is the greedy matching (match_from_counts, a pure function of the count
 matrices).  No CPU counting path exists.
 
-calculate_coco_metrics (metrics.py:197-301: bbox_mAP / segm_mAP) needs
-pycocotools and is not built.
+    calculate_coco_metrics(pred_annotations, gt_annotations)
+        -> {'bbox_mAP', 'segm_mAP'}                  # metrics.py:197-301 (COCOeval stats[0])
+
+calculate_coco_metrics is built natively, without pycocotools: COCOeval is a
+fixed, published algorithm over IoU matrices.  Masks, boxes, IoUs and the
+greedy matching of COCOeval.evaluateImg stay on the device
+(eunet_pack_masks_bbox, eunet_pairwise_overlap, eunet_coco_match); only the
+match tables come back, and coco_map_from_matches restates
+COCOeval.accumulate + summarize for stats[0] (AP@[.50:.95], all areas, 100
+detections) in numpy.  'segmentation' is a [h, w] mask where the reference
+carries an RLE, and the box always comes from the mask.  The other COCO stats,
+iscrowd and RLE decoding are not built.
 """
 from __future__ import annotations
 
+import warnings
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -211,6 +222,158 @@ def calculate_instance_metrics(pred_masks, pred_labels, pred_scores, gt_masks, g
             inter, ap, ag = np.zeros((0, len(gm)), np.int64), np.zeros(0, np.int64), np.zeros(len(gm), np.int64)
         per_class.append((inter, ap, ag, scores))
     return instance_metrics_from_counts(per_class, iou_threshold)
+
+
+# ---- COCO mAP (metrics.py:197-301: COCOeval stats[0], AP@[.50:.95], all areas, 100 detections) ------
+COCO_CLASSES = (0, 1)  # the categories of metrics.py:233-236 (0 live, 1 dead)
+COCO_MAX_DETS = 100
+# formed as pycocotools forms them (cocoeval.py, Params.setDetParams)
+COCO_IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+COCO_REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+
+
+def coco_map_from_matches(images) -> float:
+    """COCOeval.accumulate + summarize for stats[0], from the per-image match tables (pure numpy).
+
+    images: per image, in evaluation order, one entry per class of COCO_CLASSES: (scores [d] of the visited
+    detections in visiting order, matches [T][d] holding the GLOBAL id of the ground truth each detection
+    took or -1, number of ground truths).  A detection is a true positive when its match id is truthy:
+    pycocotools tests dtm for truth and the reference numbers ground truths from 0 (metrics.py:240-242), so
+    a detection matched to ground truth 0 counts as a false positive (that ground truth is still consumed).
+    Returns the mean of the precision entries > -1 over [T][recall point][class], or -1 without any."""
+    n_t, n_r = len(COCO_IOU_THRS), len(COCO_REC_THRS)
+    n_cls = len(COCO_CLASSES)
+    precision = -np.ones((n_t, n_r, n_cls))
+    for k in range(n_cls):
+        ev = [img[k] for img in images if len(img[k][0]) or img[k][2]]
+        if not ev:
+            continue
+        scores = np.concatenate([np.asarray(e[0], dtype=np.float64).reshape(-1)[:COCO_MAX_DETS] for e in ev])
+        inds = np.argsort(-scores, kind="mergesort")
+        dtm = np.concatenate([np.asarray(e[1], dtype=np.int64).reshape(n_t, -1)[:, :COCO_MAX_DETS] for e in ev],
+                             axis=1)[:, inds]
+        npig = sum(int(e[2]) for e in ev)
+        if npig == 0:
+            continue
+        tps = dtm > 0  # -1: unmatched; 0: matched to the ground truth of global id 0, falsy in pycocotools
+        tp_sum = np.cumsum(tps, axis=1).astype(dtype=float)
+        fp_sum = np.cumsum(~tps, axis=1).astype(dtype=float)
+        for t in range(n_t):
+            tp, fp = tp_sum[t], fp_sum[t]
+            nd = len(tp)
+            rc = tp / npig
+            pr = tp / (fp + tp + np.spacing(1))
+            if nd:
+                pr = np.maximum.accumulate(pr[::-1])[::-1]  # the right-to-left precision envelope
+            at = np.searchsorted(rc, COCO_REC_THRS, side="left")
+            q = np.zeros(n_r)
+            ok = at < nd  # recall points past the end keep 0 (pycocotools' try / except)
+            q[ok] = pr[at[ok]]
+            precision[t, :, k] = q
+    s = precision[precision > -1]
+    return float(np.mean(s)) if len(s) else -1.0
+
+
+def _visit_order(labels, scores):
+    """Per class, the detections in a stable sort by descending score, cut at COCO_MAX_DETS
+    (COCOeval.computeIoU / evaluateImg); the classes one after the other."""
+    scores = np.asarray(scores, dtype=np.float64)
+    labels = np.asarray(labels, dtype=np.int64)
+    order = []
+    for c in COCO_CLASSES:
+        idx = np.nonzero(labels == c)[0]
+        order.append(idx[np.argsort(-scores[idx], kind="mergesort")][:COCO_MAX_DETS])
+    return np.concatenate(order)
+
+
+def _xywh(bbox):
+    """(xmin, ymin, xmax, ymax) inclusive -> cv2.boundingRect's (x, y, w, h), on the device."""
+    out = bbox.clone()
+    out[:, 2:] = bbox[:, 2:] - bbox[:, :2] + 1
+    return out
+
+
+def coco_image_matches(pred_masks, pred_labels, pred_scores, gt_masks, gt_labels, gt_ids, device=None):
+    """One image's entries for coco_map_from_matches: (bbox entry, segm entry), each a tuple over
+    COCO_CLASSES of (scores, matches [T][d] of global ground-truth ids, number of ground truths).
+
+    With detections and ground truth present: one pack_masks_bbox per side, one pairwise_overlap over the
+    visited detections and one coco_match on the device; only the match table (and the areas, to refuse an
+    empty mask) comes back.  Without either side there is no launch."""
+    pred_labels = [int(l) for l in pred_labels]
+    gt_labels = [int(l) for l in gt_labels]
+    for l in pred_labels + gt_labels:
+        if l not in COCO_CLASSES:
+            raise ValueError(f"category_id must be one of {COCO_CLASSES}, got {l}")
+    n_t = len(COCO_IOU_THRS)
+    gt_ids = np.asarray(gt_ids, dtype=np.int64).reshape(-1)
+    n_gt = [sum(1 for l in gt_labels if l == c) for c in COCO_CLASSES]
+    scores = np.asarray([float(s) for s in pred_scores], dtype=np.float64)
+    if len(pred_labels) == 0:
+        entry = tuple((np.zeros(0), np.full((n_t, 0), -1, np.int64), n) for n in n_gt)
+        return entry, entry
+    vis = _visit_order(pred_labels, scores)
+    vis_cls = np.asarray(pred_labels, dtype=np.int64)[vis]
+    if len(gt_labels) == 0:
+        entry = tuple((scores[vis[vis_cls == c]], np.full((n_t, int((vis_cls == c).sum())), -1, np.int64), 0)
+                      for c in COCO_CLASSES)
+        return entry, entry
+    pg, ag, bg = ops.pack_masks_bbox(_stack_masks(gt_masks, device))
+    dev = pg.device
+    pp, ap, bp = ops.pack_masks_bbox(_stack_masks([pred_masks[i] for i in vis], dev))
+    inter = ops.pairwise_overlap(pp, pg)
+    match = ops.coco_match(inter, ap, ag, _xywh(bp), _xywh(bg), ops.upload(vis_cls.astype(np.int32), dev),
+                           ops.upload(np.asarray(gt_labels, dtype=np.int32), dev), COCO_IOU_THRS)
+    match = match.cpu().numpy()
+    if int(ap.min().item()) == 0 or int(ag.min().item()) == 0:
+        raise ValueError("calculate_coco_metrics: an empty mask has no bounding box (the reference divides 0 by 0)")
+    ids = np.where(match >= 0, gt_ids[np.clip(match, 0, None)], -1)  # local index -> global ground-truth id
+    out = []
+    for ty in range(2):
+        out.append(tuple((scores[vis[vis_cls == c]], ids[ty][:, vis_cls == c], n_gt[c]) for c in COCO_CLASSES))
+    return out[0], out[1]
+
+
+def calculate_coco_metrics(pred_annotations: List[Dict], gt_annotations: List[Dict]) -> Dict[str, float]:
+    """metrics.py:197-301: {'bbox_mAP', 'segm_mAP'} = COCOeval stats[0] of both IoU types.
+
+    Annotations are the reference's dicts (image_id, category_id, score for predictions) with 'segmentation'
+    a [h, w] mask (numpy array or device tensor, non-zero = set) where the reference carries a pycocotools
+    RLE.  A supplied 'bbox' is not read: the box is always cv2.boundingRect of the mask, as the reference's
+    caller forms it (train_eval.py:959, 978).  Ground-truth ids are the positions in gt_annotations; the
+    images are the sorted unique ground-truth image_ids.  Either list empty: both 0.0.  A prediction on an
+    image without ground truth: both 0.0 with a warning (COCO.loadRes asserts and the reference's except
+    returns the zeros).  An empty mask raises ValueError."""
+    metrics = {"bbox_mAP": 0.0, "segm_mAP": 0.0}
+    if not pred_annotations or not gt_annotations:
+        return metrics
+    image_ids = sorted({a["image_id"] for a in gt_annotations if "image_id" in a}) or [1]
+    default_id = image_ids[0]
+    known = set(image_ids)
+    gts = {i: [] for i in image_ids}
+    for pos, a in enumerate(gt_annotations):
+        gts[a.get("image_id", default_id)].append((pos, a))
+    preds = {i: [] for i in image_ids}
+    for a in pred_annotations:
+        iid = a.get("image_id", default_id)
+        if iid not in known:
+            warnings.warn(f"calculate_coco_metrics: a prediction on image {iid!r}, which has no ground truth; "
+                          "the reference's COCO.loadRes refuses such results, so both values are 0.0")
+            return metrics
+        preds[iid].append(a)
+    masks = [a["segmentation"] for a in list(pred_annotations) + list(gt_annotations)]
+    device = next((m.device for m in masks if isinstance(m, torch.Tensor) and m.is_cuda), None)
+    bbox_images, segm_images = [], []
+    for iid in image_ids:
+        p, g = preds[iid], [a for _, a in gts[iid]]
+        eb, es = coco_image_matches([a["segmentation"] for a in p], [a.get("category_id", 0) for a in p],
+                                    [a.get("score", 0.0) for a in p], [a["segmentation"] for a in g],
+                                    [a["category_id"] for a in g], [pos for pos, _ in gts[iid]], device)
+        bbox_images.append(eb)
+        segm_images.append(es)
+    metrics["bbox_mAP"] = coco_map_from_matches(bbox_images)
+    metrics["segm_mAP"] = coco_map_from_matches(segm_images)
+    return metrics
 
 
 # ---- viability (metrics.py:304-340) -----------------------------------------------------------------

@@ -590,6 +590,43 @@ def pack_masks(masks):
     return packed, areas
 
 
+def pack_masks_bbox(masks):
+    """pack_masks plus, from the same pass, bbox int32 [n, 4] = (xmin, ymin, xmax, ymax), inclusive, of the
+    set pixels; an empty mask gives (w, h, -1, -1)."""
+    masks = _u8(masks)
+    n, h, w = masks.shape
+    words = (h * w + 63) // 64
+    packed = torch.empty(n, words, dtype=torch.int64, device=masks.device)
+    areas = torch.empty(n, dtype=torch.int64, device=masks.device)
+    bbox = torch.empty(n, 4, dtype=torch.int32, device=masks.device)
+    call("eunet_pack_masks_bbox", _ptr(masks), n, h, w, _ptr(packed), _ptr(areas), _ptr(bbox), _stream())
+    return packed, areas, bbox
+
+
+def coco_match(inter, area_d, area_g, box_d, box_g, cls_d, cls_g, thrs):
+    """COCOeval.evaluateImg's greedy matching of one image on the device (eunet_coco_match): inter int64
+    [D, G], areas int64, boxes int32 [., 4] as (x, y, w, h), classes int32 in {0, 1}, detections in visiting
+    order; thrs a host sequence of floats.  -> match int32 [2, T, D] (0 bbox, 1 segm): the index of the ground
+    truth each detection takes, or -1.  D, G >= 1 (the caller handles the empty sides without a launch)."""
+    d, g = inter.shape
+    t = len(thrs)
+
+    def dev(x, dtype, shape):
+        if x.dtype != dtype or tuple(x.shape) != shape:
+            raise _lib.EunetError(f"coco_match: expected {dtype} {shape}, got {x.dtype} {tuple(x.shape)}")
+        return x.contiguous()
+
+    inter = dev(inter, torch.int64, (d, g))
+    area_d, area_g = dev(area_d, torch.int64, (d,)), dev(area_g, torch.int64, (g,))
+    box_d, box_g = dev(box_d, torch.int32, (d, 4)), dev(box_g, torch.int32, (g, 4))
+    cls_d, cls_g = dev(cls_d, torch.int32, (d,)), dev(cls_g, torch.int32, (g,))
+    th = (ctypes.c_double * max(t, 1))(*[float(v) for v in thrs])
+    match = torch.empty(2, t, d, dtype=torch.int32, device=inter.device)
+    call("eunet_coco_match", _ptr(inter), _ptr(area_d), _ptr(area_g), _ptr(box_d), _ptr(box_g), _ptr(cls_d),
+         _ptr(cls_g), d, g, th, t, _ptr(match), _stream())
+    return match
+
+
 def pairwise_overlap(pa, pb):
     """packed [P, words] x packed [G, words] -> inter int64 [P, G] = |a & b| per pair."""
     if pa.shape[1] != pb.shape[1]:

@@ -386,6 +386,28 @@ int eunet_probs_to_mask(const float* probs, int k, int h, int w, int64_t* mask,
  * h * w < 2^31. */
 int eunet_pack_masks(const uint8_t* masks, int n, int h, int w, uint64_t* packed, int64_t* areas,
                      void* stream);
+/* eunet_pack_masks in the same single pass plus the bounding box of the set pixels
+ * (cv2.boundingRect(mask), train_eval.py:959, 978): packed and areas as above, bbox int32
+ * [n][4] = (xmin, ymin, xmax, ymax), inclusive; an empty mask gives (w, h, -1, -1).
+ * cv2's (x, y, w, h) = (xmin, ymin, xmax - xmin + 1, ymax - ymin + 1) is formed by the caller. */
+int eunet_pack_masks_bbox(const uint8_t* masks, int n, int h, int w, uint64_t* packed,
+                          int64_t* areas, int32_t* bbox, void* stream);
+/* COCOeval.evaluateImg's greedy matching (pycocotools, behind calculate_coco_metrics,
+ * metrics.py:283-294, collected at train_eval.py:951-992) of one image: every class, both
+ * IoU types and all thresholds in one launch.  Device inputs: inter int64 [d][g] (pixel
+ * overlaps), area_d [d] / area_g [g] int64 pixel areas, box_d [d][4] / box_g [g][4] int32
+ * (x, y, w, h), 16-byte aligned, cls_d [d] / cls_g [g] int32 in {0, 1}; thrs: t doubles on
+ * the HOST.  Detections come in visiting order (per class: stable sort by descending score,
+ * cut at maxDets).  match int32 [2][t][d], type 0 bbox / 1 segm: the index (0..g-1) of the
+ * ground truth the detection takes, or -1: the untaken ground truth of the detection's class
+ * with the largest IoU >= min(thr, 1 - 1e-10), the larger index on equal IoU.  IoU in fp64:
+ * segm inter / (area_d + area_g - inter) (0 when inter == 0), bbox the integer intersection
+ * rectangle over the integer union (0 when the rectangles do not meet).  Limits: d <= 4096,
+ * g <= 8192, t <= 16.  Reads the classes back to check them: synchronises the stream. */
+int eunet_coco_match(const int64_t* inter, const int64_t* area_d, const int64_t* area_g,
+                     const int32_t* box_d, const int32_t* box_g, const int32_t* cls_d,
+                     const int32_t* cls_g, int d, int g, const double* thrs, int t, int32_t* match,
+                     void* stream);
 /* inter int64 [p][g] = sum over words of popcount(a[p][.] & b[g][.]) (np.logical_and(m1,
  * m2).sum(), metrics.py:14), zeroed by the call.  IoU = inter / (area_p + area_g - inter)
  * is formed on the host.  Masks may overlap one another. */
