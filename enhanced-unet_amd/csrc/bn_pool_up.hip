@@ -807,9 +807,8 @@ __global__ __launch_bounds__(NT) void colsum_stage2(const double* ws, int rb, in
 // unit with its coefficients in registers and strides over pixels; the block holds
 // floor(256 / U) pixels x U units (base_ch 96 -> U = 12, 21 pixels per step).
 // The per-channel constants of the BN-backward apply, gy = k1 g' + k2 y + k3 (k1 = scale = gamma
-// istd, also the forward-mask slope; kq = shift).  One function for the standalone apply below and
-// the coefficient table the fused consumers read (eunet_bn_bwd_coef -> conv3x3 dgrad staging), so
-// both round identically.
+// istd, also the forward-mask slope; kq = shift).  One function for every apply kernel below (the
+// plain one, the 1x1- and the pool-recomputing ones), so all round identically.
 struct BnBwdCoef { float k1, kq, k2, k3; };
 __device__ __forceinline__ BnBwdCoef bn_bwd_coef(float mean, float istd, float scale, float shift, float dbeta,
                                                  float dgamma, float inv_n) {
@@ -823,23 +822,11 @@ __device__ __forceinline__ BnBwdCoef bn_bwd_coef(float mean, float istd, float s
   return c;
 }
 
-__global__ void bn_bwd_coef_kernel(const float* mean, const float* istd, const float* scale, const float* shift,
-                                   const float* dbeta, const float* dgamma, float inv_n, int C, float* coef) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const BnBwdCoef k = bn_bwd_coef(mean[c], istd[c], scale[c], shift[c], dbeta[c], dgamma[c], inv_n);
-  coef[c] = k.k1;
-  coef[C + c] = k.kq;
-  coef[2 * C + c] = k.k2;
-  coef[3 * C + c] = k.k3;
-}
-
-template <typename T, typename TO, bool COEF = false>
+template <typename T, typename TO>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* g, int gct, int gco, const T* y, int yct, int yco,
                                                            long long P, int C, const float* mean, const float* istd,
                                                            const float* scale, const float* shift, const float* dbeta,
-                                                           const float* dgamma, TO* gy, int oct, int oco,
-                                                           const float* coef) {
+                                                           const float* dgamma, TO* gy, int oct, int oco) {
   constexpr int E = Vec16<T>::N;
   const int U = C / E;
   const int u = threadIdx.x % U, c = u * E;
@@ -847,14 +834,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* g, int gct, 
   float kP[E], kQ[E], k1[E], k2[E], k3[E];
 #pragma unroll
   for (int j = 0; j < E; ++j) {
-    // COEF: the table eunet_bn_bwd_coef wrote (the same bn_bwd_coef values).  A compile-time choice:
-    // with a runtime one the kernel held both paths' registers and ran 35 % slower (2.61 vs
-    // 1.93 ms/step over its 14 launches, same-box rocprofv3)
-    BnBwdCoef k;
-    if constexpr (COEF)
-      k = BnBwdCoef{coef[c + j], coef[C + c + j], coef[2 * C + c + j], coef[3 * C + c + j]};
-    else
-      k = bn_bwd_coef(mean[c + j], istd[c + j], scale[c + j], shift[c + j], dbeta[c + j], dgamma[c + j], inv_n);
+    const BnBwdCoef k = bn_bwd_coef(mean[c + j], istd[c + j], scale[c + j], shift[c + j], dbeta[c + j],
+                                    dgamma[c + j], inv_n);
     kP[j] = k.k1;
     kQ[j] = k.kq;
     k1[j] = k.k1;
@@ -1786,12 +1767,12 @@ int eunet_colsum_split(const float* part, int rows, int cols, int split, float* 
   return eunet_colsum_ld(part, rows, cols, cols, out_lo, ws, (hipStream_t)stream, split, out_hi);
 }
 
-static int bn_bwd_apply_launch(const eunet_act* g, const eunet_act* y, const float* mean, const float* invstd,
-                               const float* scale, const float* shift, const float* dbeta, const float* dgamma,
-                               const float* coef, const eunet_act* gy, void* stream) {
+int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean, const float* invstd,
+                       const float* scale, const float* shift, const float* dbeta, const float* dgamma,
+                       const eunet_act* gy, void* stream) {
   EUNET_REQUIRE(act_ok(g) && act_ok(y) && act_ok(gy) && vec_ok(g) && vec_ok(y) && vec_ok(gy),
                 "bn_bwd_apply: bad tensors");
-  EUNET_REQUIRE(coef || (mean && invstd && scale && shift && dbeta && dgamma), "bn_bwd_apply: null stats");
+  EUNET_REQUIRE(mean && invstd && scale && shift && dbeta && dgamma, "bn_bwd_apply: null stats");
   EUNET_REQUIRE(g->dtype == y->dtype && gy->dtype == y->dtype && g->c == y->c && gy->c == y->c,
                 "bn_bwd_apply: mismatch");
   const long long P = (long long)y->n * y->h * y->w;
@@ -1800,27 +1781,16 @@ static int bn_bwd_apply_launch(const eunet_act* g, const eunet_act* y, const flo
   const int bs = (256 / U) * U;
   const long long nb = (P * U + bs - 1) / bs;
   const unsigned gr = (unsigned)(nb < 4096 ? nb : 4096);
-#define EUNET_APPLY_LAUNCH(TT, CF)                                                                              \
-  bn_bwd_apply_kernel<TT, TT, CF><<<gr, bs, 0, (hipStream_t)stream>>>(                                        \
-      (const TT*)g->ptr, g->ctot, g->coff, (const TT*)y->ptr, y->ctot, y->coff, P, y->c, mean, invstd, scale, \
-      shift, dbeta, dgamma, (TT*)gy->ptr, gy->ctot, gy->coff, coef)
-  if (y->dtype == EUNET_BF16) {
-    if (coef) EUNET_APPLY_LAUNCH(bf16_t, true);
-    else EUNET_APPLY_LAUNCH(bf16_t, false);
-  } else {
-    if (coef) EUNET_APPLY_LAUNCH(float, true);
-    else EUNET_APPLY_LAUNCH(float, false);
-  }
-#undef EUNET_APPLY_LAUNCH
+  if (y->dtype == EUNET_BF16)
+    bn_bwd_apply_kernel<bf16_t, bf16_t><<<gr, bs, 0, (hipStream_t)stream>>>(
+        (const bf16_t*)g->ptr, g->ctot, g->coff, (const bf16_t*)y->ptr, y->ctot, y->coff, P, y->c, mean, invstd,
+        scale, shift, dbeta, dgamma, (bf16_t*)gy->ptr, gy->ctot, gy->coff);
+  else
+    bn_bwd_apply_kernel<float, float><<<gr, bs, 0, (hipStream_t)stream>>>(
+        (const float*)g->ptr, g->ctot, g->coff, (const float*)y->ptr, y->ctot, y->coff, P, y->c, mean, invstd,
+        scale, shift, dbeta, dgamma, (float*)gy->ptr, gy->ctot, gy->coff);
   EUNET_LAUNCH_CHECK("bn_bwd_apply");
   return EUNET_OK;
-}
-
-int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean, const float* invstd,
-                       const float* scale, const float* shift, const float* dbeta, const float* dgamma,
-                       const eunet_act* gy, void* stream) {
-  EUNET_REQUIRE(mean && invstd && scale && shift && dbeta && dgamma, "bn_bwd_apply: null stats");
-  return bn_bwd_apply_launch(g, y, mean, invstd, scale, shift, dbeta, dgamma, nullptr, gy, stream);
 }
 
 int eunet_bn_bwd_apply_1x1(const eunet_act* y, const float* w, int k, const float* gz, const float* mean,
@@ -1847,22 +1817,6 @@ int eunet_bn_bwd_apply_1x1(const eunet_act* y, const float* w, int k, const floa
         (const float*)y->ptr, y->ctot, y->coff, P, y->c, w, k, gz, mean, invstd, scale, shift, dbeta, dgamma,
         (float*)gy->ptr, gy->ctot, gy->coff);
   EUNET_LAUNCH_CHECK("bn_bwd_apply_1x1");
-  return EUNET_OK;
-}
-
-int eunet_bn_bwd_apply_coef(const eunet_act* g, const eunet_act* y, const float* coef, const eunet_act* gy,
-                            void* stream) {
-  EUNET_REQUIRE(coef, "bn_bwd_apply_coef: null coef");
-  return bn_bwd_apply_launch(g, y, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, coef, gy, stream);
-}
-
-int eunet_bn_bwd_coef(const float* mean, const float* invstd, const float* scale, const float* shift,
-                      const float* dbeta, const float* dgamma, long long count, int C, float* coef, void* stream) {
-  EUNET_REQUIRE(mean && invstd && scale && shift && dbeta && dgamma && coef && count > 0 && C > 0,
-                "bn_bwd_coef: bad args");
-  bn_bwd_coef_kernel<<<(C + 255) / 256, 256, 0, (hipStream_t)stream>>>(mean, invstd, scale, shift, dbeta, dgamma,
-                                                                       1.f / (float)count, C, coef);
-  EUNET_LAUNCH_CHECK("bn_bwd_coef");
   return EUNET_OK;
 }
 

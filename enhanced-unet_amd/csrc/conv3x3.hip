@@ -57,12 +57,6 @@ struct FwdArgs {
   const float* bmean; const float* bistd; const float* bsc; const float* bsh;
   float* bpart;
   const float* gsc;  // dgrad only, nullable: output scaled by gsc[n][co] (Dropout2d keep mask / (1-p))
-  // dgrad only, nullable: BatchNorm-backward transform of the operand (the "apply" half of BN
-  // backward, fused into the halo staging).  x holds g (gradient w.r.t. the BN+ReLU output), ty the
-  // BN's input y in tyin (same layout as x); the staged operand is gy = k1 g [y k1 + kq > 0] + k2 y + k3
-  // with tcoef = [k1 | kq | k2 | k3][cin] (eunet_bn_bwd_coef).  Co-block 0 also stores the tile
-  // interior of gy to tgo (same layout, nullable) for the weight gradient.
-  const void* tyin; const float* tcoef; void* tgo;
   int pro1;          // 1 (always, set by the launcher): the first K-chunk is staged in one round trip.
                      // Kept a runtime flag: with the halved-staging prologue still compiled in, the
                      // register allocator fits the kernel in 256 VGPRs without spills (a compile-time
@@ -83,7 +77,7 @@ constexpr int FHW = FTW + 2;                 // 34
 constexpr int FHPX = (FTH + 2) * FHW;        // 612 halo pixels
 constexpr int FHPXP = 640;                   // halo pixel slots (612 used), 4 channel quarters each
 // LDS slot (16 B) of halo pixel hp's channel quarter q.  Plane-major [q][hp] (PIX = false: the forward with
-// the BN+ReLU operand transform and the fused-apply data gradient, register staging) or pixel-major [hp][q]
+// the BN+ReLU operand transform, register staging) or pixel-major [hp][q]
 // (PIX = true: the plain data gradient and the untransformed forward, staged by LDS-DMA -- a wave-instruction then reads 16 pixels x 64 contiguous bytes from global;
 // plane-major slots would read 64 pixels x 16 B and measured slower, profiles/r04_ab.txt).  Measured per
 // layout (13 layers, tools/conv_bench.py): the forward loses 2 % pixel-major (4-way bank conflicts of the
@@ -192,8 +186,6 @@ __device__ __forceinline__ unsigned long long conv_stamp() {
 // rocprofv3 and the bench report forward and data-gradient launches separately.
 // TO: the output element type -- T, or float for a bf16 data gradient whose consumer keeps fp32
 // (the dual-branch gate backward reads the 2K-channel g_f2 in fp32; no fused BN reduction then)
-// BT: the dgrad with the BN-backward transform in its staging (eunet_conv3x3_dgrad_fused; bf16) -- its
-// own instantiation, so the plain data-gradient launches keep their register allocation.
 // BNB: the fused BN-backward reduction of the dgrad epilogue (a.bpart set) -- a template parameter so the
 // forward and the plain data-gradient launches carry none of its code.
 // PF: a bf16 forward without an operand transform (a DoubleConv's conv .0: its input is stored post-BN+ReLU)
@@ -203,7 +195,7 @@ __device__ __forceinline__ unsigned long long conv_stamp() {
 // 96 / 288-channel layers of base 96, configs[4]); that block runs a second copy of the K loop over co tiles
 // 0-1 only (half the MFMAs).  Its own instantiation: the copy's registers cost the other layers 0.2-0.5 %
 // (profiles/r05_ab.txt r5v), and a uniform branch inside the MFMA loop 2-10 % (r5u).
-template <typename T, bool DG, typename TO = T, bool BT = false, bool BNB = false, bool PF = false, bool CT = false>
+template <typename T, bool DG, typename TO = T, bool BNB = false, bool PF = false, bool CT = false>
 __global__ __launch_bounds__(FT, 2) void conv3x3_fwd_kernel(FwdArgs a) {
   constexpr int NW = 4;                       // waves
   constexpr int RPW = FTH / NW;               // output rows per wave
@@ -231,13 +223,13 @@ __global__ __launch_bounds__(FT, 2) void conv3x3_fwd_kernel(FwdArgs a) {
   char* const Bs = smem + FA_BYTES;
   constexpr int E = Vec16<T>::N, KC = KCh<T>::v;
   // this thread's halo quarter (fwd_unit), the same for every unit (ids tid + FT i)
-  constexpr bool PIX = ((DG && !BT) || PF) && sizeof(T) == 2;  // halo layout / staging (fslot)
+  constexpr bool PIX = (DG || PF) && sizeof(T) == 2;  // halo layout / staging (fslot)
   // CTE: a bf16 data gradient with a bf16 output (the plain and the BN-reducing ones) accumulates C^T (the MFMA
   // operands swapped: a lane holds 4 consecutive channels of one pixel) and stages its tile as bf16 in one pass
   // (not the CT tail instantiation: already at 254 VGPRs, the C^T epilogue spills it).  The forwards keep the C
   // layout: with C^T and their BN partials summed by DPP over a lane row the 13 standalone forwards measured
   // 0.6 % faster but the step 0.9 % slower in three alternating pairs (profiles/r06_ab.txt r6n / r6p; code in git)
-  constexpr bool CTE = DG && !BT && !CT && sizeof(T) == 2 && sizeof(TO) == 2;
+  constexpr bool CTE = DG && !CT && sizeof(T) == 2 && sizeof(TO) == 2;
   const int sq = PIX ? tid & 3 : (tid >> 3) & 3;
   const int ns = __builtin_amdgcn_readfirstlane(n);
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
@@ -245,33 +237,14 @@ __global__ __launch_bounds__(FT, 2) void conv3x3_fwd_kernel(FwdArgs a) {
       (int)((uint32_t)(a.H * a.W * a.xct) * (uint32_t)sizeof(T)), 0x00020000);
   const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
       (void*)a.wp, 0, a.nkc * KC * a.cout_pad * 9 * (int)sizeof(T), 0x00020000);
-  // dgrad: the BN-backward transform (k1 in asc, kq in ash, k2 / k3 below) and its y operand
-  constexpr int BE = DG ? E / 4 : 1;
-  f32x4 ak2[BE], ak3[BE];
-  u32x4 ry[DG ? A_IT : 1];
-  // bf16 only: the fp32 dgrad has no registers to spare (eunet_conv3x3_dgrad_fused applies the transform
-  // in a separate pass for fp32)
-  constexpr bool BTR = DG && BT && sizeof(T) == 2;
-  const bool btr = BTR && a.tcoef != nullptr;
   const uint32_t slice_bytes = (uint32_t)(a.H * a.W * a.xct) * (uint32_t)sizeof(T);
-  // the plain data gradient (no operand transform; the default schedule applies the BN backward in a
+  // the plain data gradient (no operand transform; the engine applies the BN backward in a
   // separate pass): its halo goes straight into LDS by buffer_load ... lds (wave-instruction i of wave w
   // fills slots i * FT + 64 w .. +63 = 16 pixels x 4 quarters), so a K-chunk's staging is one
   // asynchronous round trip with no staging registers
   static_assert(!PIX || A_IT * FT == 4 * FHPXP, "dma_a: whole wave-instructions over the halo slots");
-  const bool adma = PIX && !btr;
 #pragma unroll
   for (int i = 0; i < A_IT; ++i) aoff[i] = fwd_unit_off<T, PIX>(a, y0, x0, tid + i * FT);
-  const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(btr ? (const T*)a.tyin + (long long)ns * a.H * a.W * a.xct : nullptr), 0, btr ? (int)slice_bytes : 0,
-      0x00020000);
-  const __amdgpu_buffer_rsrc_t cr = __builtin_amdgcn_make_buffer_rsrc((void*)(btr ? a.tcoef : nullptr), 0,
-                                                                      btr ? 16 * a.cin : 0, 0x00020000);
-  // co-block 0 stores the staged gy (tile interior only: every pixel belongs to one tile)
-  const bool wgy = btr && a.tgo != nullptr && cob == 0;
-  const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(wgy ? (T*)a.tgo + (long long)ns * a.H * a.W * a.xct : nullptr), 0, wgy ? (int)slice_bytes : 0,
-      0x00020000);
   auto chunk_ok = [&](int kc) { return kc * KC + sq * E < a.cin; };
   auto gload_a = [&](int kc, int i0, int i1) {
     const bool cok = chunk_ok(kc);
@@ -281,8 +254,6 @@ __global__ __launch_bounds__(FT, 2) void conv3x3_fwd_kernel(FwdArgs a) {
       // a staged unit lies inside its sample slice (or is padding, read as zeros)
       EUNET_DASSERT(!cok || aoff[i] == FWD_OOB || aoff[i] + cadd + 16u <= slice_bytes);
       ra[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, cok ? aoff[i] + cadd : FWD_OOB, 0, 0);
-      if constexpr (BTR)
-        if (btr) ry[i] = __builtin_amdgcn_raw_buffer_load_b128(yr, cok ? aoff[i] + cadd : FWD_OOB, 0, 0);
     }
   };
   // BN scale / shift of this thread's channel group, through descriptors too (no branch, so
@@ -295,21 +266,10 @@ __global__ __launch_bounds__(FT, 2) void conv3x3_fwd_kernel(FwdArgs a) {
   f32x4 asc[E / 4], ash[E / 4];
   auto gload_affine = [&](int kc) {
     const uint32_t off = (uint32_t)((kc * KC + sq * E) * 4);
-    if constexpr (BTR) {
-      const uint32_t row = (uint32_t)(4 * a.cin);
 #pragma unroll
-      for (int j = 0; j < E / 4; ++j) {
-        asc[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(cr, off + 16 * j, 0, 0));
-        ash[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(cr, row + off + 16 * j, 0, 0));
-        ak2[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(cr, 2 * row + off + 16 * j, 0, 0));
-        ak3[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(cr, 3 * row + off + 16 * j, 0, 0));
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < E / 4; ++j) {
-        asc[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sr, off + 16 * j, 0, 0));
-        ash[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(hr, off + 16 * j, 0, 0));
-      }
+    for (int j = 0; j < E / 4; ++j) {
+      asc[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sr, off + 16 * j, 0, 0));
+      ash[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(hr, off + 16 * j, 0, 0));
     }
   };
   auto lwrite_a = [&](int kc, int i0, int i1) {
@@ -320,21 +280,7 @@ __global__ __launch_bounds__(FT, 2) void conv3x3_fwd_kernel(FwdArgs a) {
       fwd_unit<PIX>(tid + i * FT, hp, qq);
       if (hp >= FHPX) continue;
       u32x4 v = ra[i];
-      if constexpr (DG) {
-        if (BTR && btr) {  // BN backward of the layer whose input gradient this is; padding stays zero
-          float f[E], yv[E];
-          Vec16<T>::unpack(__builtin_bit_cast(uint4, v), f);
-          Vec16<T>::unpack(__builtin_bit_cast(uint4, ry[i]), yv);
-          const bool ok = cok && aoff[i] < FWD_OOB;
-#pragma unroll
-          for (int j = 0; j < E; ++j) {
-            const float k1 = asc[j >> 2][j & 3];
-            const float gg = fmaf(yv[j], k1, ash[j >> 2][j & 3]) > 0.f ? f[j] : 0.f;  // the forward's ReLU mask
-            f[j] = ok ? fmaf(k1, gg, fmaf(yv[j], ak2[j >> 2][j & 3], ak3[j >> 2][j & 3])) : 0.f;
-          }
-          v = __builtin_bit_cast(u32x4, Vec16<T>::pack(f));
-        }
-      } else if (a.isc != nullptr) {  // BN + ReLU of the producing layer; padding stays zero
+      if (!DG && a.isc != nullptr) {  // BN + ReLU of the producing layer; padding stays zero
         const bool ok = cok && aoff[i] < FWD_OOB;
         if constexpr (sizeof(T) == 2) {
           // packed fp32 FMA per bf16 pair, rounded to bf16, ReLU on the rounded pair (sign bit:
@@ -429,50 +375,21 @@ __global__ __launch_bounds__(FT, 2) void conv3x3_fwd_kernel(FwdArgs a) {
   if (blockIdx.x & 1) __builtin_amdgcn_s_sleep(40);
   auto stage_halves = [&](int kc) {
     dma_b(kc);
-    if (PIX && adma) {
+    if (PIX) {
       dma_a(kc);
       return;
     }
     gload_affine(kc);
-    if (DG && btr) {  // two loads per halo unit (g and y): thirds bound the staging registers
-      constexpr int A3 = (A_IT + 2) / 3;
-      gload_a(kc, 0, A3);
-      lwrite_a(kc, 0, A3);
-      gload_a(kc, A3, 2 * A3);
-      lwrite_a(kc, A3, 2 * A3);
-      gload_a(kc, 2 * A3, A_IT);
-      lwrite_a(kc, 2 * A3, A_IT);
-    } else {
-      gload_a(kc, 0, AH);
-      lwrite_a(kc, 0, AH);
-      gload_a(kc, AH, A_IT);
-      lwrite_a(kc, AH, A_IT);
-    }
-  };
-  // co-block 0 of the fused BN-backward dgrad stores the tile interior of the staged gy (for the
-  // weight gradient) from LDS right before the chunk's MFMAs, so the stores drain under them instead
-  // of holding the next staging loads' vmcnt waits: 2048 units = 16 x 32 px x 4 channel quarters
-  auto store_gy = [&](int kc) {
-    if constexpr (BTR) {
-      constexpr int SU = FTH * FTW * 4 / FT;  // 8 units per thread
-#pragma unroll 1
-      for (int j = 0; j < SU; ++j) {
-        const int u = tid + j * FT;            // (pixel row, quarter, pixel column): coalesced stores
-        const int px = u & (FTW - 1), qq = (u >> 5) & 3, py = u >> 7;
-        const int yy = y0 + py, xx = x0 + px;
-        const bool ok = yy < a.H && xx < a.W && kc * KC + qq * E < a.cin;
-        const u32x4 v = *(const u32x4*)(As + fslot<PIX>((py + 1) * FHW + px + 1, qq) * 16);
-        const uint32_t off = ok ? (uint32_t)(((yy * a.W + xx) * a.xct + a.xco + kc * KC + qq * E) * (int)sizeof(T)) : FWD_OOB;
-        EUNET_DASSERT(!ok || off + 16u <= slice_bytes);
-        __builtin_amdgcn_raw_buffer_store_b128(v, gr, off, 0, 0);
-      }
-    }
+    gload_a(kc, 0, AH);
+    lwrite_a(kc, 0, AH);
+    gload_a(kc, AH, A_IT);
+    lwrite_a(kc, AH, A_IT);
   };
 #if CONV_STAMP
   unsigned long long st_t0 = conv_stamp(), st_stage = 0, st_mfma = 0, st_a, st_b;
   st_a = st_t0;
 #endif
-  if (PIX && adma) {
+  if (PIX) {
     stage_halves(0);
   } else if (a.pro1) {  // first chunk in one round trip: the accumulators are not live yet
     dma_b(0);
@@ -483,7 +400,6 @@ __global__ __launch_bounds__(FT, 2) void conv3x3_fwd_kernel(FwdArgs a) {
     stage_halves(0);
   }
   __syncthreads();
-  if (wgy) store_gy(0);
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -500,7 +416,6 @@ __global__ __launch_bounds__(FT, 2) void conv3x3_fwd_kernel(FwdArgs a) {
       __syncthreads();  // every wave is done reading the stage
       stage_halves(kc);
       __syncthreads();
-      if (wgy) store_gy(kc);
 #if CONV_STAMP
       st_b = conv_stamp();
       st_stage += st_b - st_a;
@@ -1485,7 +1400,7 @@ int elems16(int dtype) { return dtype == EUNET_BF16 ? 8 : 4; }
 int kchunk(int dtype) { return 4 * elems16(dtype); }
 
 template <bool DG>
-int launch_fwd(const FwdArgs& a, int dtype, void* stream, bool out_f32 = false, bool bt = false) {
+int launch_fwd(const FwdArgs& a, int dtype, void* stream, bool out_f32 = false) {
   const long long esz = dtype == EUNET_BF16 ? 2 : 4;
   EUNET_REQUIRE((long long)a.H * a.W * a.xct * esz < (long long)FWD_OOB,
                 "conv3x3: one sample's input (%d x %d x %d) must be < 3 GiB (buffer-descriptor staging)", a.H, a.W, a.xct);
@@ -1499,24 +1414,21 @@ int launch_fwd(const FwdArgs& a, int dtype, void* stream, bool out_f32 = false, 
   };
   if (dtype == EUNET_BF16 && out_f32) {
     go(conv3x3_fwd_kernel<bf16_t, true, float>);
-  } else if (dtype == EUNET_BF16 && DG && bt) {
-    if (bnb) go(conv3x3_fwd_kernel<bf16_t, true, bf16_t, true, true>);
-    else go(conv3x3_fwd_kernel<bf16_t, true, bf16_t, true, false>);
   } else if (dtype == EUNET_BF16) {
     const int tail = a.cout % BN;
     if (tail > 0 && tail <= BN / 2) {  // a half-empty tail co-block: the CT instantiations
-      if (bnb) go(conv3x3_fwd_kernel<bf16_t, true, bf16_t, false, true, false, true>);
-      else if (!DG && a.isc == nullptr) go(conv3x3_fwd_kernel<bf16_t, false, bf16_t, false, false, true, true>);
-      else go(conv3x3_fwd_kernel<bf16_t, DG, bf16_t, false, false, false, true>);
+      if (bnb) go(conv3x3_fwd_kernel<bf16_t, true, bf16_t, true, false, true>);
+      else if (!DG && a.isc == nullptr) go(conv3x3_fwd_kernel<bf16_t, false, bf16_t, false, true, true>);
+      else go(conv3x3_fwd_kernel<bf16_t, DG, bf16_t, false, false, true>);
     } else if (bnb) {
-      go(conv3x3_fwd_kernel<bf16_t, true, bf16_t, false, true>);
+      go(conv3x3_fwd_kernel<bf16_t, true, bf16_t, true>);
     } else if (!DG && a.isc == nullptr) {
-      go(conv3x3_fwd_kernel<bf16_t, false, bf16_t, false, false, true>);
+      go(conv3x3_fwd_kernel<bf16_t, false, bf16_t, false, true>);
     } else {
       go(conv3x3_fwd_kernel<bf16_t, DG>);
     }
   } else {
-    if (bnb) go(conv3x3_fwd_kernel<float, true, float, false, true>);
+    if (bnb) go(conv3x3_fwd_kernel<float, true, float, true>);
     else go(conv3x3_fwd_kernel<float, DG>);
   }
   EUNET_LAUNCH_CHECK("conv3x3_fwd");
@@ -1598,7 +1510,6 @@ int eunet_conv3x3_fwd(const eunet_act* x, const float* in_scale, const float* in
   a.stats = stats; a.tx = cdiv(x->w, FTW); a.ty = cdiv(x->h, FTH); a.ntiles = x->n * a.tx * a.ty;
   a.by = nullptr; a.byct = 0; a.byco = 0;
   a.bmean = a.bistd = a.bsc = a.bsh = nullptr; a.bpart = nullptr; a.gsc = nullptr;
-  a.tyin = nullptr; a.tcoef = nullptr; a.tgo = nullptr;
   a.pro1 = 1;
   EUNET_REQUIRE(y->c % E == 0 && y->ctot % E == 0 && y->coff % E == 0,
                 "conv3x3_fwd: output channels/stride/offset must be multiples of %d", E);
@@ -1625,7 +1536,6 @@ int eunet_conv3x3_dgrad(const eunet_act* dy, const void* wp_t, const eunet_act* 
   a.stats = nullptr; a.tx = cdiv(dy->w, FTW); a.ty = cdiv(dy->h, FTH); a.ntiles = dy->n * a.tx * a.ty;
   a.by = nullptr; a.byct = 0; a.byco = 0;
   a.bmean = a.bistd = a.bsc = a.bsh = nullptr; a.bpart = nullptr; a.gsc = gscale;
-  a.tyin = nullptr; a.tcoef = nullptr; a.tgo = nullptr;
   a.pro1 = 1;
   return launch_fwd<true>(a, dy->dtype, stream, out_f32);
 }
@@ -1652,57 +1562,8 @@ int eunet_conv3x3_dgrad_bnbwd(const eunet_act* dy, const void* wp_t, const eunet
   a.stats = nullptr; a.tx = cdiv(dy->w, FTW); a.ty = cdiv(dy->h, FTH); a.ntiles = dy->n * a.tx * a.ty;
   a.by = y->ptr; a.byct = y->ctot; a.byco = y->coff;
   a.bmean = mean; a.bistd = invstd; a.bsc = scale; a.bsh = shift; a.bpart = part; a.gsc = gscale;
-  a.tyin = nullptr; a.tcoef = nullptr; a.tgo = nullptr;
   a.pro1 = 1;
   return launch_fwd<true>(a, dy->dtype, stream);
-}
-
-int eunet_conv3x3_dgrad_fused(const eunet_act* g, const eunet_act* y_in, const float* coef, const eunet_act* gy_out,
-                              const void* wp_t, const eunet_act* gx, const eunet_act* y_next, const float* mean,
-                              const float* invstd, const float* scale, const float* shift, float* part,
-                              const float* gscale, void* stream) {
-  EUNET_REQUIRE(act_ok(g) && act_ok(y_in) && coef && act_ok(gx) && wp_t, "conv3x3_dgrad_fused: bad args");
-  EUNET_REQUIRE(g->dtype == gx->dtype && y_in->dtype == g->dtype, "conv3x3_dgrad_fused: dtype mismatch");
-  EUNET_REQUIRE(g->n == gx->n && g->h == gx->h && g->w == gx->w, "conv3x3_dgrad_fused: spatial mismatch");
-  // y_in (and gy_out) are addressed with g's unit offsets: the same shape and channel layout
-  EUNET_REQUIRE(y_in->n == g->n && y_in->h == g->h && y_in->w == g->w && y_in->c == g->c && y_in->ctot == g->ctot &&
-                    y_in->coff == g->coff,
-                "conv3x3_dgrad_fused: y_in must have g's shape and channel layout");
-  if (gy_out)
-    EUNET_REQUIRE(act_ok(gy_out) && gy_out->dtype == g->dtype && gy_out->n == g->n && gy_out->h == g->h &&
-                      gy_out->w == g->w && gy_out->c == g->c && gy_out->ctot == g->ctot && gy_out->coff == g->coff,
-                  "conv3x3_dgrad_fused: gy_out must have g's shape and channel layout");
-  const bool red = y_next != nullptr;
-  EUNET_REQUIRE(red == (part != nullptr) && (!red || (act_ok(y_next) && mean && invstd && scale && shift)),
-                "conv3x3_dgrad_fused: the next-BN reduction needs y_next, mean, invstd, scale, shift and part");
-  if (red)
-    EUNET_REQUIRE(y_next->dtype == gx->dtype && y_next->n == gx->n && y_next->h == gx->h && y_next->w == gx->w &&
-                      y_next->c == gx->c,
-                  "conv3x3_dgrad_fused: y_next shape mismatch");
-  const int E = elems16(g->dtype);
-  EUNET_REQUIRE(g->c % E == 0 && g->ctot % E == 0 && g->coff % E == 0 && gx->c % E == 0 && gx->ctot % E == 0 &&
-                    gx->coff % E == 0 && (!red || (y_next->ctot % E == 0 && y_next->coff % E == 0)),
-                "conv3x3_dgrad_fused: channels/strides must be multiples of %d", E);
-  FwdArgs a;
-  a.x = g->ptr; a.N = g->n; a.H = g->h; a.W = g->w; a.xct = g->ctot; a.xco = g->coff; a.cin = g->c;
-  a.isc = nullptr; a.ish = nullptr; a.iss = 0;
-  a.wp = wp_t; a.cout_pad = cdiv(gx->c, BN) * BN; a.nkc = cdiv(g->c, kchunk(g->dtype));
-  a.bias = nullptr;
-  a.y = gx->ptr; a.yct = gx->ctot; a.yco = gx->coff; a.cout = gx->c;
-  a.stats = nullptr; a.tx = cdiv(g->w, FTW); a.ty = cdiv(g->h, FTH); a.ntiles = g->n * a.tx * a.ty;
-  a.by = red ? y_next->ptr : nullptr; a.byct = red ? y_next->ctot : 0; a.byco = red ? y_next->coff : 0;
-  a.bmean = mean; a.bistd = invstd; a.bsc = scale; a.bsh = shift; a.bpart = part; a.gsc = gscale;
-  a.tyin = y_in->ptr; a.tcoef = coef; a.tgo = gy_out ? gy_out->ptr : nullptr;
-  a.pro1 = 1;
-  if (g->dtype != EUNET_BF16) {
-    // fp32: the transform runs as its own pass into gy_out (the fp32 staging has no registers for
-    // it), then the plain data gradient reads gy_out -- the same values
-    EUNET_REQUIRE(gy_out, "conv3x3_dgrad_fused: fp32 needs gy_out (the transform is materialised)");
-    const int rc = eunet_bn_bwd_apply_coef(g, y_in, coef, gy_out, stream);
-    if (rc != EUNET_OK) return rc;
-    a.x = gy_out->ptr; a.tyin = nullptr; a.tcoef = nullptr; a.tgo = nullptr;
-  }
-  return launch_fwd<true>(a, g->dtype, stream, false, a.tcoef != nullptr);
 }
 
 

@@ -80,14 +80,6 @@ def side_stream(device) -> torch.cuda.Stream:
     return _SIDE[key]
 
 
-def _per_block(flag, nm) -> bool:
-    """An engine knob that is a collection of block names, or any other value taken as a bool (every
-    block or none: True / False / 0 / 1)."""
-    if isinstance(flag, (set, frozenset, list, tuple)):
-        return nm in flag
-    return bool(flag)
-
-
 class UNetEngine:
     """One BasicUNet trunk (+ the enhance head for the single-branch model).  prefix names the
     trunk's parameters in the owning module ('model.' for EnhancedUNet, 'unetpp.' / 'deeplab.'
@@ -108,59 +100,17 @@ class UNetEngine:
     #     +2.1 % img/s (profiles/r02_ab_za.txt; round 1's opposite result: profiles/r01_ab_za.txt)
     #   True: one elementwise pass on the main stream; conv .3's forward and wgrad read za as is
     materialize_za = False
-    # fuse_bn_reduce -- a block's BN-b backward reduction fused into the kernel producing its output
-    # gradient (upsample / max-pool / 1x1 adjoints) instead of a separate bn_bwd_reduce pass
-    fuse_bn_reduce = True
-    # wg3_late -- conv .3's weight gradient joins the side stream after the block's BN-a backward
-    # rather than before conv .3's data gradient: the side stream's wgrad blocks hold whole CUs
-    # (256 VGPRs x 8 waves), and bn_bwd_apply on the critical launch stream waited for CU slots;
-    # this way the wgrad overlaps conv .0's data gradient instead.  A/B +0.6 % img/s, 6 of 7
-    # alternating pairs on one box (profiles/r02_ab_conv.txt)
-    wg3_late = True
-    # wg3_early_last -- in the trunk's last block (no input gradient, so no conv .0 data gradient follows
-    # to overlap), conv .3's weight gradient joins the side stream as soon as its dY is ready instead of
-    # running at the step's tail (profiles/r04_step_timeline.txt).  Measured neutral (173.0-174.7 vs
-    # 173.6-174.2 img/s, three alternating pairs, profiles/r04_ab.txt): off
-    wg3_early_last = False
-    # fuse_bn_apply -- the apply half of the DoubleConv's second BatchNorm backward (gy = k1 g' + k2
-    # y + k3) inside conv .3's data-gradient operand staging (eunet_conv3x3_dgrad_fused), which also
-    # stores gy for conv .3's weight gradient.  Same values, bit for bit, but measured slower: the
-    # dgrad's staging carries two loads per halo unit, the transform and the gy stores while the
-    # standalone apply streams at ~4.9 TB/s beside the side stream's weight gradients -- 26.0-26.1 vs
-    # 25.3-25.5 ms/step in three alternating same-box rounds (profiles/r03_ab.txt).  Off by default.
-    # A set of block names ({"enc4", "dec4"}) fuses those blocks only.
-    fuse_bn_apply = False
-    # fuse_bn_apply_a -- the same for the first BatchNorm (conv .0's data gradient; needs
-    # fuse_bn_apply).  Off: conv .0's weight gradient then has to wait for that dgrad and overlaps the
-    # next level's HBM-bound upsample / max-pool adjoints instead of the dgrad (they ran 2.7x longer:
-    # +0.85 ms/step in a same-box A/B, profiles/r03_ab.txt)
-    fuse_bn_apply_a = False
     # dec1_recompute -- dec1's input gradient W^T g_z (64 channels at H) is not stored: conv1x1_bwd only
     # reduces it for dec2's second BatchNorm, and that BatchNorm's apply recomputes it per pixel from g_z
     # (eunet_bn_bwd_apply_1x1: the same gy bit for bit, 2 x 537 MB less HBM traffic at the bench shape).
-    # Needs fuse_bn_reduce and dec2 outside fuse_bn_apply (whose fused dgrad reads the stored gradient).
     dec1_recompute = True
     # pool_recompute -- the same for the encoders' output gradients gskip + maxpool-adjoint(gpool):
     # pool_bwd_add_bnr only reduces them, the block's apply recomputes them per 2x2 window
-    # (eunet_bn_bwd_apply_pool: the same gy bit for bit, 0.75 C per pixel less traffic).  Needs
-    # fuse_bn_reduce, the block outside fuse_bn_apply, and even H and W at the level.  Round 5 measured it
+    # (eunet_bn_bwd_apply_pool: the same gy bit for bit, 0.75 C per pixel less traffic).  H and W
+    # are even at every level it runs at: forward_trunk requires multiples of 8.  Round 5 measured it
     # equal (182.4 vs 182.7 img/s, profiles/r05_ab.txt r5pr); with round 6's weight gradient it is +0.3 / +1.0 %
     # in two same-box runs of three alternating rounds each (profiles/r06_ab.txt r6pr): on
     pool_recompute = True
-    # dgrad_first -- after a DoubleConv's BN-a backward, conv .0's data gradient is issued on the launch
-    # stream before the side-stream weight gradients (which wait on an event recorded right after the
-    # apply, not on the launch stream's tail).  Closes half of the ~24 us apply -> dgrad launch-stream gap
-    # per block, but the dgrads then take the CUs first and the squeezed weight gradients spread over the
-    # HBM-bound kernels: step time unchanged in a same-box A/B (+0.1 %), the conv family's wall-time
-    # fraction 0.369 -> 0.341 (profiles/r03_ab.txt).  Off by default.
-    dgrad_first = False
-    # fork_once -- after a DoubleConv's BN-a backward, the side stream's three waits on the launch stream
-    # (conv .3's and conv .0's weight gradients, the bucket hook) share one event recorded there, instead of
-    # one wait_stream each (each record is a marker packet the launch stream's next kernel, conv .0's data
-    # gradient, queues behind: ~21 us per block).  Measured slower: 173.6-174.1 vs 175.5-176.6 img/s in four
-    # alternating pairs (profiles/r04_ab.txt) -- like dgrad_first, a data gradient that reaches the CUs
-    # before the side stream's weight gradients costs the step more than the gap.  Off.
-    fork_once = False
     # device_fence_forks -- the side stream's forks and joins wait through eunet_stream_wait (events with a
     # device-scope release) instead of torch's Stream.wait_stream (a system-scope release: an L2 writeback
     # and invalidate on the launch stream at every fork)
@@ -378,27 +328,16 @@ class UNetEngine:
                              bn["shift"], dbeta, dgamma, ops.act(gy))
             return gy
 
-        def dgrad0(gya):  # conv .0's data gradient (the block's input gradient)
-            wpt = S["wp"].get(p + ".0.weight^T") if S.get("wp") else None
-            if wpt is None:
-                wpt = ops.conv3x3_pack(P[p + ".0.weight"], dt, flip=True)
-            gx = _e((N, H, W, X.c), dt, dev)
-            ops.conv3x3_dgrad(ops.act(gya), wpt, ops.act(gx))
-            return gx
-
         main = torch.cuda.current_stream(dev)
         side = side_stream(dev) if self.overlap_wgrad else None
 
-        def wgrad(conv, xa: ops.Act, gy, scale=None, shift=None, small_conv=False, on_main=False, ready=None):
+        def wgrad(conv, xa: ops.Act, gy, scale=None, shift=None, small_conv=False, on_main=False):
             # the gradient slots are allocated on the launch stream (their consumers run there)
             dw = sink.slot(conv + ".weight", (C, xa.c, 3, 3))
             db = sink.slot(conv + ".bias", (C,))
             if side is None or on_main:
                 return wgrad_on_stream(xa, gy, dw, db, scale, shift, small_conv)
-            if ready is not None:
-                side.wait_event(ready)  # recorded on the launch stream once gy was complete
-            else:
-                self._wait(side, main)  # gy (and everything before it) is ready
+            self._wait(side, main)  # gy (and everything before it) is ready
             with torch.cuda.stream(side):
                 wgrad_on_stream(xa, gy, dw, db, scale, shift, small_conv)
             for t in (gy, xa._keep, dw, db):  # the caching allocator must not hand these out early
@@ -419,118 +358,29 @@ class UNetEngine:
                 ops.conv3x3_wgrad(xa, gya, dwp, dbp, ns, scale=scale, shift=shift)
             ops.wgrad_reduce(dwp, dbp, ns, C, cin, 9, dw, db)
 
-        if _per_block(self.fuse_bn_apply, nm):
-            return self._block_bwd_fused(nm, G, S, P, sink, need_gx, small, gred, wgrad, side, main)
-        gyb = bn_back(p + ".4", G, yb, bnb, part=gred[0], tiles=gred[1])
+        def packed(conv):  # the conv's transposed + flipped weight, from the forward's pack when it is there
+            wpt = S["wp"].get(conv + ".weight^T") if S.get("wp") else None
+            return wpt if wpt is not None else ops.conv3x3_pack(P[conv + ".weight"], dt, flip=True)
 
-        def wgrad3():
-            if s.get("za") is not None:
-                wgrad(p + ".3", ops.act(s["za"]), gyb)
-            else:
-                wgrad(p + ".3", ops.act(ya), gyb, bna["scale"], bna["shift"])
-        early3 = not self.wg3_late or (self.wg3_early_last and not need_gx)
-        if early3:
-            wgrad3()
-        wpt = S["wp"].get(p + ".3.weight^T") if S.get("wp") else None
-        if wpt is None:
-            wpt = ops.conv3x3_pack(P[p + ".3.weight"], dt, flip=True)
+        gyb = bn_back(p + ".4", G, yb, bnb, part=gred[0], tiles=gred[1])
+        wpt = packed(p + ".3")
         gaa = torch.empty_like(ya)
         ctiles = ops.conv3x3_tiles(ops.act(gaa))
         cpart = _e(ctiles * 2 * C, torch.float32, dev)
         ops.conv3x3_dgrad_bnbwd(ops.act(gyb), wpt, ops.act(gaa), ops.act(ya), bna["mean"], bna["invstd"],
                                 bna["scale"], bna["shift"], cpart)
         gya = bn_back(p + ".1", gaa, ya, bna, part=cpart, tiles=ctiles)
-        ev = None
-        gx = None
-        if side is not None and (self.fork_once or (self.dgrad_first and need_gx)):
-            ev = torch.cuda.Event()
-            ev.record(main)  # gyb, gya and the BN-parameter gradients are complete
-            if self.dgrad_first and need_gx:
-                gx = dgrad0(gya)
-        if not early3:
-            if s.get("za") is not None:
-                wgrad(p + ".3", ops.act(s["za"]), gyb, ready=ev)
-            else:
-                wgrad(p + ".3", ops.act(ya), gyb, bna["scale"], bna["shift"], ready=ev)
+        # conv .3's weight gradient joins the side stream here, after the BN-a backward, so that it
+        # overlaps conv .0's data gradient and not bn_bwd_apply on the critical launch stream
+        if s.get("za") is not None:
+            wgrad(p + ".3", ops.act(s["za"]), gyb)
+        else:
+            wgrad(p + ".3", ops.act(ya), gyb, bna["scale"], bna["shift"])
         del gyb
         # the trunk's last weight gradient (no data gradient follows it): on the main stream, which is
         # otherwise idle here, instead of queueing behind the side stream's conv .3 wgrad
-        wgrad(p + ".0", X, gya, small_conv=small, on_main=not need_gx, ready=ev)
+        wgrad(p + ".0", X, gya, small_conv=small, on_main=not need_gx)
         del gaa
-        names = [f"{p}.{i}.{w}" for i in (0, 1, 3, 4) for w in ("weight", "bias")]
-        if side is None:
-            sink.ready(names)
-        else:  # a bucket all-reduce launched here orders after both streams' work, without stalling main
-            if ev is not None:
-                side.wait_event(ev)
-            else:
-                self._wait(side, main)
-            with torch.cuda.stream(side):
-                sink.ready(names)
-        if not need_gx:
-            return None
-        return gx if gx is not None else dgrad0(gya)
-
-    def _block_bwd_fused(self, nm, G, S, P, sink, need_gx, small, gred, wgrad, side, main):
-        """_block_bwd with each BN backward's apply fused into the data gradient that consumes it:
-        colsum -> (dbeta, dgamma) -> coefficient table; the dgrad stages gy = k1 g' + k2 y + k3 from
-        (g, y) and stores it for the weight gradient, which therefore follows its dgrad."""
-        p = f"{self.prefix}{nm}"
-        s = S[nm]
-        ya, yb, bna, bnb, X = s["ya"], s["yb"], s["bna"], s["bnb"], s["X"]
-        N, H, W, C = yb.shape
-        dev, dt = yb.device, self.dtype
-
-        def bn_coef(prefix, g, y, bn, part=None, tiles=0):
-            if part is None:  # reduction not fused into the producer of g
-                tiles = ops.bn_bwd_tiles(ops.act(y))
-                part = _e(tiles * 2 * C, torch.float32, dev)
-                ops.bn_bwd_reduce(ops.act(g), ops.act(y), bn["mean"], bn["invstd"], bn["scale"],
-                                  bn["shift"], part)
-            dbeta, dgamma = sink.slot(prefix + ".bias", (C,)), sink.slot(prefix + ".weight", (C,))
-            ops.colsum(part, tiles, 2 * C, dbeta, split=C, out_hi=dgamma)
-            coef = _e(4 * C, torch.float32, dev)
-            ops.bn_bwd_coef(bn["mean"], bn["invstd"], bn["scale"], bn["shift"], dbeta, dgamma, N * H * W, coef)
-            return coef
-
-        def packed(conv):
-            wpt = S["wp"].get(conv + ".weight^T") if S.get("wp") else None
-            return wpt if wpt is not None else ops.conv3x3_pack(P[conv + ".weight"], dt, flip=True)
-
-        coefb = bn_coef(p + ".4", G, yb, bnb, part=gred[0], tiles=gred[1])
-        gyb = torch.empty_like(yb)
-        gaa = torch.empty_like(ya)
-        ctiles = ops.conv3x3_tiles(ops.act(gaa))
-        cpart = _e(ctiles * 2 * C, torch.float32, dev)
-        ops.conv3x3_dgrad_fused(ops.act(G), ops.act(yb), coefb, ops.act(gyb), packed(p + ".3"), ops.act(gaa),
-                                ops.act(ya), bna["mean"], bna["invstd"], bna["scale"], bna["shift"], cpart)
-
-        def wgrad3():
-            if s.get("za") is not None:
-                wgrad(p + ".3", ops.act(s["za"]), gyb)
-            else:
-                wgrad(p + ".3", ops.act(ya), gyb, bna["scale"], bna["shift"])
-        early3 = not self.wg3_late or (self.wg3_early_last and not need_gx)
-        if early3:
-            wgrad3()
-        coefa = bn_coef(p + ".1", gaa, ya, bna, part=cpart, tiles=ctiles)
-        if self.wg3_late:
-            wgrad3()
-        del gyb
-        gya = torch.empty_like(ya)
-        gx = None
-        if need_gx and _per_block(self.fuse_bn_apply_a, nm):
-            gx = _e((N, H, W, X.c), dt, dev)
-            ops.conv3x3_dgrad_fused(ops.act(gaa), ops.act(ya), coefa, ops.act(gya), packed(p + ".0"), ops.act(gx))
-            wgrad(p + ".0", X, gya, small_conv=small)
-        else:  # gy materialised; conv .0's weight gradient overlaps its data gradient (round 2's order)
-            ops.bn_bwd_apply_coef(ops.act(gaa), ops.act(ya), coefa, ops.act(gya))
-            # the trunk's last weight gradient (no data gradient follows it): on the then idle main stream
-            wgrad(p + ".0", X, gya, small_conv=small, on_main=not need_gx)
-            if need_gx:
-                gx = _e((N, H, W, X.c), dt, dev)
-                ops.conv3x3_dgrad(ops.act(gya), packed(p + ".0"), ops.act(gx))
-        del gaa, gya
         names = [f"{p}.{i}.{w}" for i in (0, 1, 3, 4) for w in ("weight", "bias")]
         if side is None:
             sink.ready(names)
@@ -538,6 +388,11 @@ class UNetEngine:
             self._wait(side, main)
             with torch.cuda.stream(side):
                 sink.ready(names)
+        if not need_gx:
+            return None
+        wpt = packed(p + ".0")
+        gx = _e((N, H, W, X.c), dt, dev)  # conv .0's data gradient (the block's input gradient)
+        ops.conv3x3_dgrad(ops.act(gya), wpt, ops.act(gx))
         return gx
 
     def backward(self, S, g_out: torch.Tensor, sink: Optional[GradSink] = None):
@@ -581,7 +436,7 @@ class UNetEngine:
 
         def up_bwd(ghi: ops.Act, glo: torch.Tensor, nm):
             """g w.r.t. block nm's output from the upsample adjoint, its BN-b reduction fused."""
-            rows = ops.upsample_bwd_bnr_rows(ops.act(glo)) if self.fuse_bn_reduce else 0
+            rows = ops.upsample_bwd_bnr_rows(ops.act(glo))
             if not rows:
                 ops.upsample_bwd(ghi, ops.act(glo))
                 return None, 0
@@ -592,14 +447,13 @@ class UNetEngine:
         def pool_bwd(act_saved: ops.Act, gpool: ops.Act, gskip: ops.Act, shape, nm):
             """block nm's output gradient (a tensor, or GradPool when the apply recomputes it) and the
             (part, rows) of its fused BN-b reduction."""
-            rows = ops.pool_bwd_add_bnr_rows(act_saved) if self.fuse_bn_reduce else 0  # (gout's shape)
+            rows = ops.pool_bwd_add_bnr_rows(act_saved)  # (gout's shape)
             if not rows:
                 gout = _e(shape, dt, dev)
                 ops.pool_bwd_add(act_saved, gpool, gskip, ops.act(gout))
                 return gout, (None, 0)
             part = _e(rows * 2 * shape[3], torch.float32, dev)
-            if (self.pool_recompute and not _per_block(self.fuse_bn_apply, nm) and shape[1] % 2 == 0
-                    and shape[2] % 2 == 0):
+            if self.pool_recompute:  # (H and W are even here: forward_trunk requires multiples of 8)
                 ops.pool_bwd_add_bnr(act_saved, gpool, gskip, None, *bnr_args(nm), part)
                 return GradPool(gpool, gskip), (part, rows)
             gout = _e(shape, dt, dev)
@@ -613,21 +467,16 @@ class UNetEngine:
         part = _e(tiles * (K * b + K), torch.float32, dev)
         w1 = P[pre + "dec1.weight"].reshape(K, b).contiguous()
         bnb2 = s2["bnb"]
-        red2 = (None, 0)
-        if self.fuse_bn_reduce:
-            bpart = _e(tiles * 2 * b, torch.float32, dev)
-            if self.dec1_recompute and not _per_block(self.fuse_bn_apply, "dec2"):
-                gd2 = Grad1x1(w1, K, gz)
-                ops.conv1x1_bwd_bnr(yb_act, bnb2["scale"], bnb2["shift"], w1, K, gz, None, part,
-                                    bnb2["mean"], bnb2["invstd"], bpart)
-            else:
-                gd2 = torch.empty_like(s2["yb"])
-                ops.conv1x1_bwd_bnr(yb_act, bnb2["scale"], bnb2["shift"], w1, K, gz, ops.act(gd2), part,
-                                    bnb2["mean"], bnb2["invstd"], bpart)
-            red2 = (bpart, tiles)
+        bpart = _e(tiles * 2 * b, torch.float32, dev)
+        if self.dec1_recompute:
+            gd2 = Grad1x1(w1, K, gz)
+            ops.conv1x1_bwd_bnr(yb_act, bnb2["scale"], bnb2["shift"], w1, K, gz, None, part,
+                                bnb2["mean"], bnb2["invstd"], bpart)
         else:
             gd2 = torch.empty_like(s2["yb"])
-            ops.conv1x1_bwd(yb_act, bnb2["scale"], bnb2["shift"], w1, K, gz, ops.act(gd2), part)
+            ops.conv1x1_bwd_bnr(yb_act, bnb2["scale"], bnb2["shift"], w1, K, gz, ops.act(gd2), part,
+                                bnb2["mean"], bnb2["invstd"], bpart)
+        red2 = (bpart, tiles)
         # the column sums go straight into the two gradient slots (colsum's split output)
         ops.colsum(part, tiles, K * b + K, sink.slot(pre + "dec1.weight", (K, b, 1, 1)), split=K * b,
                    out_hi=sink.slot(pre + "dec1.bias", (K,)))

@@ -295,8 +295,7 @@ class Trainer:
         return self.optimizer.param_groups[0]["lr"]
 
 
-ENGINE_KNOBS = ("overlap_wgrad", "materialize_za", "fuse_bn_reduce", "wg3_late", "fuse_bn_apply", "fuse_bn_apply_a",
-                "dgrad_first", "wg3_early_last", "fork_once", "dec1_recompute", "pool_recompute", "device_fence_forks",
+ENGINE_KNOBS = ("overlap_wgrad", "materialize_za", "dec1_recompute", "pool_recompute", "device_fence_forks",
                 "narrow_mfma")
 
 
@@ -304,12 +303,7 @@ def _engine_knobs(eng):
     """Every schedule knob a captured step depends on: the engine's, and for the dual-branch engine its
     two trunk engines' too (their knobs are UNetEngine class attributes unless set per instance)."""
     engines = [eng] + [getattr(eng, n) for n in ("ea", "eb") if hasattr(eng, n)]
-    return tuple(tuple(_hashable(getattr(e, k, None)) for k in ENGINE_KNOBS) for e in engines)
-
-
-def _hashable(v):
-    """A per-block knob (a set of block names) as a sorted tuple, for the graph key."""
-    return tuple(sorted(v)) if isinstance(v, (set, frozenset, list)) else v
+    return tuple(tuple(getattr(e, k, None) for k in ENGINE_KNOBS) for e in engines)
 
 
 class StepGraph:

@@ -231,9 +231,9 @@ def test_network_ops_registered_with_the_dispatcher():
     """The network's device ops are torch.ops.eunet.* (SURVEY.md §8b): one schema per C-ABI entry point, the
     written arguments alias-annotated, CPU tensors rejected (no CPU fallback) through the dispatcher too."""
     from eunet import EunetError, ops
-    expect = {"conv3x3_fwd", "conv3x3_dgrad", "conv3x3_dgrad_bnbwd", "conv3x3_dgrad_fused", "conv3x3_wgrad",
+    expect = {"conv3x3_fwd", "conv3x3_dgrad", "conv3x3_dgrad_bnbwd", "conv3x3_wgrad",
               "wgrad_reduce", "conv_small_fwd", "conv_small_wgrad", "bn_finalize", "bnrelu_pool", "bnrelu_upsample",
-              "bnrelu_conv1x1", "head_fwd", "head_bwd", "bn_bwd_apply", "bn_bwd_coef", "bn_bwd_apply_coef",
+              "bnrelu_conv1x1", "head_fwd", "head_bwd", "bn_bwd_apply",
               "pool_bwd_add_bnr", "upsample_bwd_bnr", "conv1x1_bwd_bnr", "bn_bwd_apply_1x1", "bn_bwd_apply_pool",
               "colsum", "conv3x3_pack"}
     assert expect <= set(ops.DISPATCHED)
@@ -242,7 +242,7 @@ def test_network_ops_registered_with_the_dispatcher():
     assert "Tensor(b!)? stats" in sch
     assert str(torch.ops.eunet.conv3x3_pack.default._schema).endswith("-> Tensor")
     with pytest.raises(EunetError):
-        torch.ops.eunet.bn_bwd_coef(*[torch.zeros(4)] * 6, 16, torch.zeros(16))
+        torch.ops.eunet.bn_eval_affine(*[torch.zeros(4)] * 4, 1e-5, torch.zeros(4), torch.zeros(4))
 
 
 def test_opt_table_layout_and_supported():

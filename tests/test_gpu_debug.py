@@ -1,7 +1,7 @@
 """The bounds-checked debug build (libeunet_hip_debug.so, -DEUNET_DEBUG), run once:
 in a child process whose EUNET_LIB points at it, a deliberately failing device check is reported
 (unit and line), and then full training steps of the single- and dual-branch models (bf16 and
-fp32, ragged tile edges, multi-split weight gradients, the fused BN-backward staging) trip none of
+fp32, ragged tile edges, multi-split weight gradients, the LDS-DMA halo staging) trip none of
 the device-side checks on staging offsets, tile / split indices and output addresses."""
 import os
 import subprocess

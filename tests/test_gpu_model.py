@@ -325,25 +325,21 @@ def test_materialised_activation_is_exact(dtype, monkeypatch):
 
 
 def test_backward_stream_schedules_are_exact(monkeypatch):
-    """The weight gradients on the side stream (conv .3's enqueued early or after the block's BN-a
-    backward, UNetEngine.wg3_late; conv .0's data gradient issued before or after them,
-    UNetEngine.dgrad_first) or all on the launch stream run the same kernels on the same operands:
-    every gradient agrees bit for bit."""
+    """The weight gradients on the side stream (UNetEngine.overlap_wgrad, the default) or all on the
+    launch stream run the same kernels on the same operands: every gradient agrees bit for bit."""
     from eunet import engine, synth
     from eunet.losses import combined_loss
     x, msk = synth.batch(2, 64, 64, start_index=5, num_classes=2, in_channels=1)
     out = {}
-    for overlap, late, first in ((True, True, True), (True, True, False), (True, False, True), (False, True, True)):
-        monkeypatch.setattr(engine.UNetEngine, "wg3_late", late)
+    for overlap in (True, False):
         monkeypatch.setattr(engine.UNetEngine, "overlap_wgrad", overlap)
-        monkeypatch.setattr(engine.UNetEngine, "dgrad_first", first)
         m = _model(16, 1, 2, "bf16")
         m.train()
         loss = combined_loss(m.forward_lowres(x.to(DEV)), msk.to(DEV))
         loss.backward()
         torch.cuda.synchronize()
-        out[(overlap, late, first)] = {k: p.grad.detach().clone() for k, p in m.named_parameters()}
-    ref = out[(True, True, True)]
+        out[overlap] = {k: p.grad.detach().clone() for k, p in m.named_parameters()}
+    ref = out[True]
     for key, grads in out.items():
         for k, g in grads.items():
             assert torch.equal(g, ref[k]), (key, k)
@@ -474,65 +470,6 @@ def test_bf16_train_grads_vs_fp64_oracle():
     head = {r[1]: r[2] for r in rows if r[1].startswith("enhance.")}
     print("bf16 head parameter gradients, rel L2 vs fp64:", head)
     assert all(e < HEAD_BF16_GRAD_TOL for e in head.values()), head
-
-
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_fused_bn_apply_schedule_is_exact(dtype, monkeypatch):
-    """UNetEngine.fuse_bn_apply (BN-backward apply inside the data-gradient staging, weight
-    gradients reading the gy it stores) against the separate bn_bwd_apply passes: the loss and
-    every parameter gradient agree bit for bit, with the weight gradients on the side stream or
-    on the launch stream."""
-    from eunet import engine, synth
-    from eunet.losses import combined_loss
-    x, msk = synth.batch(2, 96, 64, start_index=13, num_classes=2, in_channels=1)
-    out = {}
-    deep = frozenset({"enc3", "enc4", "dec4"})  # per-block fusion (UNetEngine.fuse_bn_apply as a set)
-    for fused, fused_a, overlap in ((True, False, True), (True, True, True), (False, False, True),
-                                    (True, True, False), (deep, False, True), (deep, deep, True)):
-        monkeypatch.setattr(engine.UNetEngine, "fuse_bn_apply", fused)
-        monkeypatch.setattr(engine.UNetEngine, "fuse_bn_apply_a", fused_a)
-        monkeypatch.setattr(engine.UNetEngine, "overlap_wgrad", overlap)
-        m = _model(32, 1, 2, dtype)
-        m.train()
-        loss = combined_loss(m.forward_lowres(x.to(DEV)), msk.to(DEV))
-        loss.backward()
-        torch.cuda.synchronize()
-        out[(fused, fused_a, overlap)] = (loss.item(), {k: p.grad.detach().clone() for k, p in m.named_parameters()})
-    ref = out[(False, False, True)]
-    for key, (lv, grads) in out.items():
-        assert lv == ref[0], key
-        for k, g in grads.items():
-            assert torch.equal(g, ref[1][k]), (key, k)
-
-
-@pytest.mark.parametrize("dtype", ["bf16"])
-def test_wgrad_schedule_knobs_are_exact(dtype, monkeypatch):
-    """UNetEngine.wg3_late / wg3_early_last / dgrad_first / fork_once only move conv .3's weight gradient
-    between the launch and side streams, change the issue order or the events the side stream waits on:
-    loss and every parameter gradient bit for bit."""
-    from eunet import engine, synth
-    from eunet.losses import combined_loss
-    x, msk = synth.batch(2, 96, 64, start_index=17, num_classes=2, in_channels=1)
-    out = {}
-    for late, early_last, dfirst, fonce in ((True, True, False, True), (True, False, False, True),
-                                            (False, False, False, True), (True, True, True, True),
-                                            (True, False, False, False), (True, False, True, False)):
-        monkeypatch.setattr(engine.UNetEngine, "wg3_late", late)
-        monkeypatch.setattr(engine.UNetEngine, "wg3_early_last", early_last)
-        monkeypatch.setattr(engine.UNetEngine, "dgrad_first", dfirst)
-        monkeypatch.setattr(engine.UNetEngine, "fork_once", fonce)
-        m = _model(32, 1, 2, dtype)
-        m.train()
-        loss = combined_loss(m.forward_lowres(x.to(DEV)), msk.to(DEV))
-        loss.backward()
-        torch.cuda.synchronize()
-        out[(late, early_last, dfirst, fonce)] = (loss.item(),
-                                                  {k: p.grad.detach().clone() for k, p in m.named_parameters()})
-    ref = out[(True, False, False, False)]
-    for key, (lv, grads) in out.items():
-        assert lv == ref[0], key
-        for k, g in grads.items():
-            assert torch.equal(g, ref[1][k]), (key, k)
 
 
 def _graph_batches(n, H=64, W=96, B=2):

@@ -1,7 +1,7 @@
 """Run bench.py's main() with UNetEngine schedule attributes overridden (same-box A/B of engine
 choices without environment knobs in the product):
 
-    python tools/ab_attr.py fuse_bn_apply=0 wg3_late=1 -- --steps 30 --warmup 5 --no-cpu-baseline ...
+    python tools/ab_attr.py pool_recompute=0 materialize_za=1 -- --steps 30 --warmup 5 --no-cpu-baseline ...
 """
 import os
 import sys
@@ -21,8 +21,6 @@ for kv in sets:
     elif k.startswith("dual."):  # DualEngine attributes (e.g. dual.narrow_mfma=0)
         from eunet.dual import DualEngine
         setattr(DualEngine, k[5:], bool(int(v)))
-    elif v.startswith("{"):  # a per-block knob: fuse_bn_apply={enc4,dec4}
-        setattr(UNetEngine, k, frozenset(x for x in v.strip("{}").split(",") if x))
     else:
         setattr(UNetEngine, k, bool(int(v)))
 import bench  # noqa: E402

@@ -1,6 +1,6 @@
 """bench.py with UNetEngine class attributes overridden, for schedule A/Bs on the GPU box:
 
-    python tools/bench_knob.py wg3_early_last=0 [knob=value ...] -- [bench.py arguments]
+    python tools/bench_knob.py pool_recompute=0 [knob=value ...] -- [bench.py arguments]
 
 Values are Python literals (0/1/True/False).  Runs bench.py in this process (runpy), nothing else."""
 import ast

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of UNetEngine knob settings on the default bench workload, alternating rounds.
-#   VARIANTS="base|fuse_bn_apply={enc4,dec4}|arg:--step-graph 1" ROUNDS=3 bash tools/gpu_ab_knobs.sh
+#   VARIANTS="base|pool_recompute=0|arg:--step-graph 1" ROUNDS=3 bash tools/gpu_ab_knobs.sh
 # ("base" = no override, "arg:..." = extra bench arguments); one JSON line per run in gpurun_out/ab_<tag>.jsonl
 set -u
 mkdir -p gpurun_out
