@@ -1125,39 +1125,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1))) void bn
 }
 
 
-template <typename T, typename TO>
-__global__ void up_bwd_kernel(const T* g, int gct, int gco, TO* o, int oct, int oco, int N, int h, int w, int C) {
-  constexpr int E = Vec16<T>::N;
-  const int U = C / E, H2 = 2 * h, W2 = 2 * w;
-  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= (long long)N * h * w * U) return;
-  const int u = (int)(id % U);
-  long long p = id / U;
-  const int x = (int)(p % w); p /= w;
-  const int y = (int)(p % h);
-  const int n = (int)(p / h);
-  const int c = u * E;
-  float acc[E];
-#pragma unroll
-  for (int j = 0; j < E; ++j) acc[j] = 0.f;
-  for (int oy = 2 * y - 1; oy <= 2 * y + 2; ++oy) {
-    if (oy < 0 || oy >= H2) continue;
-    const float wy = up2_adj_w(oy, h, y);
-    if (wy == 0.f) continue;
-    for (int ox = 2 * x - 1; ox <= 2 * x + 2; ++ox) {
-      if (ox < 0 || ox >= W2) continue;
-      const float wx = up2_adj_w(ox, w, x);
-      if (wx == 0.f) continue;
-      float f[E];
-      Vec16<T>::unpack(*(const uint4*)(g + ((long long)(n * H2 + oy) * W2 + ox) * gct + gco + c), f);
-      const float ww = wy * wx;
-#pragma unroll
-      for (int j = 0; j < E; ++j) acc[j] = fmaf(ww, f[j], acc[j]);
-    }
-  }
-  *(uint4*)(o + ((long long)(n * h + y) * w + x) * oct + oco + c) = Vec16<TO>::pack(acc);
-}
-
 // Upsample x2 adjoint, separable, as a row sweep: a thread owns low-res columns x0, x0+1 of one
 // 16-byte channel unit over UP_R low-res rows.  Each high-res row r of its 6-column window is
 // reduced horizontally once (H_b[r] = sum_dx wx_b(dx) g[r][2 x0 - 1 + dx]) and weighted into the
@@ -1596,6 +1563,9 @@ int eunet_conv_small_wgrad(const eunet_act* x, const eunet_act* dy, float* dw_pa
                            void* stream) {
   EUNET_REQUIRE(act_ok(x) && act_ok(dy) && dw_part && nsplit > 0, "conv_small_wgrad: bad args");
   EUNET_REQUIRE(x->c <= SCI && x->dtype == dy->dtype, "conv_small_wgrad: Cin <= 8, equal dtypes");
+  // the dY tile is staged in whole 16-byte units
+  EUNET_REQUIRE(vec_ok(dy), "conv_small_wgrad: dy channels, slot and row stride must be multiples of a 16-byte unit");
+  EUNET_REQUIRE(x->n == dy->n && x->h == dy->h && x->w == dy->w, "conv_small_wgrad: spatial mismatch");
   SmallWgArgs a;
   a.x = x->ptr; a.N = x->n; a.H = x->h; a.W = x->w; a.xct = x->ctot; a.xco = x->coff; a.cin = x->c;
   a.dy = dy->ptr; a.dct = dy->ctot; a.dco = dy->coff; a.cout = dy->c;

@@ -127,6 +127,8 @@ int eunet_wgrad_reduce(const float* dw_part, const float* db_part, int nsplit, i
 int eunet_conv_small_fwd(const eunet_act* x, const float* w, const float* bias,
                          const eunet_act* y, float* stats, void* stream);
 int eunet_conv_small_wgrad_splits(const eunet_act* dy, int* nsplit);
+/* dy is read in whole 16-byte units: dy->c, dy->ctot and dy->coff must be multiples of 8 (bf16) / 4
+ * (fp32), and x and dy must agree in n, h, w; anything else is EUNET_ERR_INVALID */
 int eunet_conv_small_wgrad(const eunet_act* x, const eunet_act* dy, float* dw_part,
                            float* db_part, int nsplit, void* stream);
 
