@@ -9,6 +9,7 @@ is not importable, models.py:71-76, 304-314):
     EnhancedUNet(num_classes=3).forward(x) -> [B,K,2H,2W]     # models.py:246-343
     EnhancedUNet.get_aux_outputs() -> None                    # models.py:341-343
     state_dict keys: model.enc1.0.weight ... enhance.3.bias   # 109 keys (c3, K3)
+    UNet(num_classes=3).forward(x) -> [B,K,2H,2W]             # models.py:175-243, 100 keys
 
 Build-side keyword-only generalisations (BASELINE configs): in_channels,
 base_ch, dtype ('fp32' | 'bf16' compute/storage of activations; parameters,
@@ -24,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from .dual import DualEngine, DualFunction, dual_backward_order
+from .baselines import PlainUNetEngine
 from .engine import UNetEngine, UNetFunction
 
 _DTYPES = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
@@ -51,13 +53,67 @@ class _UNetParams(nn.Module):
         self.dec1 = nn.Conv2d(b, num_classes, 1)
 
 
-class UNet(nn.Module):
-    """Reference UNet wrapper (models.py:175-243), SMP-absent: holds BasicUNet as .model."""
+def _check_limits(num_classes: int, in_channels: int, base_ch: int):
+    if not 1 <= num_classes <= 3:
+        raise ValueError("num_classes must be 1..3 (the reference loss tables have 3 classes)")
+    if in_channels > 4:
+        raise ValueError("in_channels must be <= 4")
+    if base_ch % 16:
+        raise ValueError("base_ch must be a multiple of 16")
 
-    def __init__(self, num_classes: int = 3, *, in_channels: int = 3, base_ch: int = 64):
-        super().__init__()
+
+class _EngineModel(nn.Module):
+    """What a baseline model needs around its engine: the engine call in its four modes (train / eval, with and
+    without grad -- as EnhancedUNet._run), dtype switching and the data-parallel sink hook."""
+
+    def _setup(self, num_classes, in_channels, base_ch, dtype):
+        _check_limits(num_classes, in_channels, base_ch)
         self.num_classes = num_classes
+        self.in_channels = in_channels
+        self.base_ch = base_ch
+        self.compute_dtype = _DTYPES[dtype]
+        self.grad_sink_factory = None  # set by eunet.dp for bucketed all-reduce overlap
+
+    def set_dtype(self, dtype: str):
+        self.compute_dtype = _DTYPES[dtype]
+        self._engine.dtype = self.compute_dtype
+        return self
+
+    def _run(self, x: torch.Tensor, want: str) -> torch.Tensor:
+        if self.training:
+            if torch.is_grad_enabled():
+                return UNetFunction.apply(x, want, self._engine, self.grad_sink_factory,
+                                          *[p for _, p in self.named_parameters()])
+            with torch.no_grad():
+                return self._engine.forward(x, training=True, want=want)[0]
+        with torch.no_grad():
+            return self._engine.forward(x, training=False, want=want)[0]
+
+    def get_aux_outputs(self):
+        return None
+
+
+class UNet(_EngineModel):
+    """Reference UNet wrapper (models.py:175-243), SMP-absent: holds BasicUNet as .model; the
+    Enhanced-UNet trunk without the enhance head, on the same engine."""
+
+    def __init__(self, num_classes: int = 3, *, in_channels: int = 3, base_ch: int = 64, dtype: str = "fp32"):
+        super().__init__()
+        self._setup(num_classes, in_channels, base_ch, dtype)
         self.model = _UNetParams(in_channels, base_ch, num_classes)
+        self._engine = PlainUNetEngine(self)
+
+    def backward_param_order(self):
+        return None  # eunet.dp's default order (dec1, dec2 ... enc1) is this engine's
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B,C,H,W] -> logits [B,K,2H,2W] (models.py:227-237: BasicUNet ends with an upsample)."""
+        return self._run(x, "out2h")
+
+    def forward_lowres(self, x: torch.Tensor) -> torch.Tensor:
+        """forward + the training loop's 2H->H bilinear resize (train_eval.py:306-310, an exact 2x2
+        mean): logits [B,K,H,W] without materialising the 2H output."""
+        return self._run(x, "logits")
 
 
 class EnhancedUNet(nn.Module):
@@ -149,10 +205,14 @@ class EnhancedUNet(nn.Module):
 
 def get_model(model_name: str, num_classes: int = 3, device: str = "cuda", train_mode: bool = False,
               data_dir: str = None, max_size: int = 640, **kwargs):
-    """models.py:590-624.  Only the Enhanced-UNet hot path is built here; the other
-    reference nets are out of scope (SURVEY.md §2 #15) and raise like unknown names."""
+    """models.py:590-624.  Built here: 'enhanced_unet', and the baseline made of the same ops, 'unet'
+    (BasicUNet: the Enhanced-UNet trunk without the enhance head).  The other reference nets ('segnet',
+    'fcn', 'pspnet', 'linknet') are not built and raise like unknown names.  kwargs: the
+    build's keywords (in_channels, base_ch, dtype)."""
     if model_name == "enhanced_unet":
         return EnhancedUNet(num_classes=num_classes, **kwargs)
     if model_name == "unet":
-        raise ValueError("unet (SMP resnet50 / BasicUNet) is out of scope of this build; use 'enhanced_unet'")
+        return UNet(num_classes=num_classes, **kwargs)
+    if model_name in ("segnet", "fcn", "pspnet", "linknet"):
+        raise ValueError(f"{model_name} is out of scope of this build (DESIGN.md §7); use 'enhanced_unet' or 'unet'")
     raise ValueError(f"Unknown model: {model_name}")

@@ -324,6 +324,36 @@ def bnrelu_conv1x1(y: Act, scale, shift, w, b, k, z):
          _stream())
 
 
+KTAIL_UP2, KTAIL_SMOOTH = 0, 1  # EUNET_KTAIL_*
+
+
+def _ktail_check(name, t, shape):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise _lib.EunetError(f"{name}: need a contiguous fp32 tensor of shape {tuple(shape)}, got "
+                              f"{t.dtype} {tuple(t.shape)}")
+
+
+@_dispatched("i T T!")
+def ktail_fwd(mode, z_lo, out):
+    """z_lo [N,h,w,K] NHWC fp32 -> out NCHW fp32: [N,K,2h,2w] = up2(z_lo) (KTAIL_UP2) or
+    [N,K,h,w] = mean2x2(up2(z_lo)) (KTAIL_SMOOTH)."""
+    n, h, w, k = z_lo.shape
+    s = 2 if mode == KTAIL_UP2 else 1
+    _ktail_check("ktail_fwd z_lo", z_lo, (n, h, w, k))
+    _ktail_check("ktail_fwd out", out, (n, k, s * h, s * w))
+    call("eunet_ktail_fwd", int(mode), _ptr(z_lo), n, h, w, k, _ptr(out), _stream())
+
+
+@_dispatched("i T T!")
+def ktail_bwd(mode, g, gz_lo):
+    """The adjoints of ktail_fwd: g NCHW -> gz_lo [N,h,w,K]."""
+    n, h, w, k = gz_lo.shape
+    s = 2 if mode == KTAIL_UP2 else 1
+    _ktail_check("ktail_bwd g", g, (n, k, s * h, s * w))
+    _ktail_check("ktail_bwd gz_lo", gz_lo, (n, h, w, k))
+    call("eunet_ktail_bwd", int(mode), _ptr(g), n, h, w, k, _ptr(gz_lo), _stream())
+
+
 def head_workspace_bytes(n, h, w, k, dtype=torch.float32):
     b = c_size_t()
     call("eunet_head_workspace_bytes", n, h, w, k, DTYPES[dtype], ctypes.byref(b))

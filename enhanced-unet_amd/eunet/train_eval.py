@@ -34,25 +34,35 @@ from .losses import CrossEntropyLoss, FocalLoss, check_targets, combined_loss, c
 from .models import EnhancedUNet
 
 
+# train_eval.py:82-119: loss-term weights, auxiliary supervision and base learning rate per model name
+# ('unet' takes the reference's default row)
+TRAINER_TABLE = {
+    "enhanced_unet": dict(dice=2.5, focal=2.5, tversky=1.0, aux={"unetpp": 0.6, "deeplab": 0.5}, consistency=0.4,
+                          lr=4e-3),
+    "unet": dict(dice=1.5, focal=1.5, tversky=0.5, aux={}, consistency=0.0, lr=2e-3),
+}
+
+
 class Trainer:
     def __init__(self, model, device, model_name, total_epochs: int = 50):
         self.model = model
         self.device = device
         self.model_name = model_name
         self.total_epochs = max(1, total_epochs)
-        if model_name != "enhanced_unet":
-            raise ValueError("this build implements the enhanced_unet training path only")
+        if model_name not in TRAINER_TABLE:
+            raise ValueError(f"this build implements the training paths of {sorted(TRAINER_TABLE)} only")
+        row = TRAINER_TABLE[model_name]
         # train_eval.py:74-80: the focal and CE modules with the reference's class weights
         class_weights = torch.tensor([1.0, 20.0, 10.0]).to(device)
         alpha = [1.0, 8.0, 5.0]
         self.focal_loss = FocalLoss(alpha=alpha, gamma=5.0, ignore_index=None, class_weights=class_weights)
         self.ce_loss = CrossEntropyLoss(weight=class_weights)
-        self.dice_loss_weight = 2.5
-        self.focal_loss_weight = 2.5
-        self.tversky_loss_weight = 1.0
-        self.aux_branch_weights = {"unetpp": 0.6, "deeplab": 0.5}
-        self.consistency_weight = 0.4
-        base_lr = 4e-3
+        self.dice_loss_weight = row["dice"]
+        self.focal_loss_weight = row["focal"]
+        self.tversky_loss_weight = row["tversky"]
+        self.aux_branch_weights = dict(row["aux"])
+        self.consistency_weight = row["consistency"]
+        base_lr = row["lr"]
         params = [p for p in model.parameters()]
         try:
             self.optimizer = torch.optim.AdamW(params, lr=base_lr, weight_decay=1e-4, betas=(0.9, 0.999),
@@ -240,7 +250,7 @@ class Trainer:
             fused = self.model(images)
             loss = self.aux_loss(fused, self.model.get_aux_outputs(), masks)
         else:
-            if isinstance(self.model, EnhancedUNet):
+            if hasattr(self.model, "forward_lowres"):
                 logits = self.model.forward_lowres(images)
             else:
                 out = self.model(images)

@@ -164,6 +164,19 @@ int eunet_bnrelu_upsample(const eunet_act* y, const float* scale, const float* s
 int eunet_bnrelu_conv1x1(const eunet_act* y, const float* scale, const float* shift,
                          const float* w, const float* b, int k, float* z, void* stream);
 
+/* ---- baseline network unet (models.py:175-243, SMP-absent BasicUNet) -------------------------------
+ * The K-channel (K = 1..3) fp32 tails behind the 1x1 head.  z_lo [N,h,w,K] NHWC fp32, out NCHW fp32.
+ *   EUNET_KTAIL_UP2:    out [N,K,2h,2w] = up2(z_lo), bilinear x2, align_corners=False: the final
+ *                       upsample of UNet.forward (models.py:236, dec1 commuted before it)
+ *   EUNET_KTAIL_SMOOTH: out [N,K,h,w] = mean2x2(up2(z_lo)): the training loop's 2H -> H bilinear
+ *                       resize of the unet output (train_eval.py:306-310), computed as the separable
+ *                       (1/8, 3/4, 1/8) filter with replicate edges */
+enum { EUNET_KTAIL_UP2 = 0, EUNET_KTAIL_SMOOTH = 1 };
+int eunet_ktail_fwd(int mode, const float* z_lo, int n, int h, int w, int k, float* out, void* stream);
+/* their adjoints (autograd of the above): g NCHW ([N,K,2h,2w] for UP2, [N,K,h,w] for SMOOTH) ->
+ * gz_lo [N,h,w,K] NHWC */
+int eunet_ktail_bwd(int mode, const float* g, int n, int h, int w, int k, float* gz_lo, void* stream);
+
 /* ---- enhance head at 2H + residual + 2x2 mean (models.py:308-313,336-337;
  *      train_eval.py:306-310 resize == 2x2 mean) ------------------------------
  * z: [N,H,W,K] fp32. out2h (nullable) [N,K,2H,2W] fp32 NCHW, logits
@@ -254,7 +267,7 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
  * eunet_debug_enabled: 1 in the debug build, 0 in the release library (where the checks compile away).
  * eunet_debug_status: synchronises the device; *count = failed checks since the last reset,
  * *unit_line = unit * 100000 + source line of the first (units: 1 capi, 2 conv3x3, 3 bn_pool_up,
- * 4 head, 5 instances; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
+ * 4 head, 5 instances, 6 baselines; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
 int eunet_debug_enabled(void);
 int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset);
 int eunet_debug_selftest(void* stream);
