@@ -73,6 +73,12 @@ SIGNATURES = {
     "eunet_bnrelu": [_P, _f, _f, _P, c_void_p],
     "eunet_bnrelu_pool": [_P, _f, _f, _P, _P, c_void_p],
     "eunet_bnrelu_upsample": [_P, _f, _f, _P, c_void_p],
+    "eunet_upconv2x2_packed_bytes": [c_int, c_int, POINTER(c_size_t)],
+    "eunet_upconv2x2_pack": [_f, c_int, _f, c_int, c_void_p],
+    "eunet_bnrelu_upconv2x2_fwd": [_P, _f, _f, _f, _f, _P, c_void_p],
+    "eunet_upconv2x2_dgrad": [_P, _f, _P, c_void_p],
+    "eunet_upconv2x2_wgrad_splits": [_P, c_int, POINTER(c_int)],
+    "eunet_upconv2x2_wgrad": [_P, _f, _f, _P, _f, _f, c_int, c_void_p],
     "eunet_bnrelu_conv1x1": [_P, _f, _f, _f, _f, c_int, _f, c_void_p],
     "eunet_ktail_fwd": [c_int, _f, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_ktail_bwd": [c_int, _f, c_int, c_int, c_int, c_int, _f, c_void_p],

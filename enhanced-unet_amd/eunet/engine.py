@@ -4,6 +4,10 @@ Reference structure (models.py:199-240, 304-339):
     e1 = enc1(x); e2 = enc2(pool(e1)); e3 = enc3(pool(e2)); e4 = enc4(pool(e3))
     d4 = dec4(cat[up(e4), e3]); d3 = dec3(cat[up(d4), e2]); d2 = dec2(cat[up(d3), e1])
     out = u + enhance(u),  u = dec1(up(d2))  (== up(dec1(d2)), computed that way)
+up = bilinear x2 (the reference), or -- a model built with upsample="transpose" -- for the three trunk
+upsamples above a learned ConvTranspose2d(C, C, 2, stride=2) (model.up4 / up3 / up2, upconv.hip).  The
+last upsample, behind dec1, is bilinear in both: the commutation dec1(up(d2)) = up(dec1(d2)) that the
+head / ktail kernels rely on holds only for a per-channel linear upsample.
 
 Data layout in HBM (NHWC, dtype = fp32 or bf16):
   * each DoubleConv keeps only its two PRE-BatchNorm conv outputs y_a, y_b;
@@ -30,6 +34,7 @@ from ._lib import EunetError
 ENCODER_SCOPE = "conv3x3.encoder_train"  # kprof family of every encoder conv3x3 launch (fwd, dgrad, wgrad)
 
 BLOCKS = ("enc1", "enc2", "enc3", "enc4", "dec4", "dec3", "dec2")
+UPCONVS = ("up4", "up3", "up2")  # the learned upsamples of a transpose model: enc4 -> dec4, dec4 -> dec3, dec3 -> dec2
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 class Grad1x1:
@@ -134,6 +139,7 @@ class UNetEngine:
         self.K = model.num_classes
         self.cin = model.in_channels
         self.dtype = model.compute_dtype
+        self.transpose = getattr(model, "upsample", "bilinear") == "transpose"
 
     # ------------------------------------------------------------------ utils
     def _P(self):
@@ -250,6 +256,8 @@ class UNetEngine:
         S = {}
         wps = self._pack_all(P, training)
         S["wp"] = wps
+        if self.transpose:  # packed once per step: the forward's and the data gradient's operands
+            S["up"] = {u: ops.upconv2x2_pack(P[f"{self.prefix}{u}.weight"], dt) for u in UPCONVS}
         xin = _e((N, H, W, Cin), dt, dev)
         ops.nchw_to_nhwc(x.contiguous().float(), xin)
         cat4 = _e((N, *lv[2], ch[3] + ch[2]), dt, dev)
@@ -265,8 +273,12 @@ class UNetEngine:
             ops.bnrelu_pool(ops.act(s["yb"]), s["bnb"]["scale"], s["bnb"]["shift"],
                             ops.act(cat, coff, s["yb"].shape[3]), ops.act(pooled))
 
-        def consume_up(nm, cat):
+        def consume_up(nm, cat, up):
             s = S[nm]
+            if self.transpose:
+                ops.bnrelu_upconv2x2(ops.act(s["yb"]), s["bnb"]["scale"], s["bnb"]["shift"], S["up"][up],
+                                     P[f"{self.prefix}{up}.bias"], ops.act(cat, 0, s["yb"].shape[3]))
+                return
             ops.bnrelu_upsample(ops.act(s["yb"]), s["bnb"]["scale"], s["bnb"]["shift"],
                                 ops.act(cat, 0, s["yb"].shape[3]))
 
@@ -277,11 +289,11 @@ class UNetEngine:
         S["enc3"] = self._block_fwd("enc3", ops.act(p2), training, P, B, small=False, wps=wps)
         consume_pool("enc3", cat4, ch[3], p3)
         S["enc4"] = self._block_fwd("enc4", ops.act(p3), training, P, B, small=False, wps=wps)
-        consume_up("enc4", cat4)
+        consume_up("enc4", cat4, "up4")
         S["dec4"] = self._block_fwd("dec4", ops.act(cat4), training, P, B, small=False, wps=wps)
-        consume_up("dec4", cat3)
+        consume_up("dec4", cat3, "up3")
         S["dec3"] = self._block_fwd("dec3", ops.act(cat3), training, P, B, small=False, wps=wps)
-        consume_up("dec3", cat2)
+        consume_up("dec3", cat2, "up2")
         S["dec2"] = self._block_fwd("dec2", ops.act(cat2), training, P, B, small=False, wps=wps)
         s = S["dec2"]
         z = _e((N, H, W, K), torch.float32, dev)
@@ -434,8 +446,41 @@ class UNetEngine:
             s = S[nm]
             return (ops.act(s["yb"]), s["bnb"]["mean"], s["bnb"]["invstd"], s["bnb"]["scale"], s["bnb"]["shift"])
 
-        def up_bwd(ghi: ops.Act, glo: torch.Tensor, nm):
+        def upconv_bwd(ghi: ops.Act, glo: torch.Tensor, nm, up):
+            """The learned upsample's backward: the data gradient (w.r.t. block nm's post-ReLU output; the block's
+            BN backward reduces it unfused) on the launch stream, the weight / bias gradient on the side stream."""
+            s = S[nm]
+            C = glo.shape[3]
+            ops.upconv2x2_dgrad(ghi, S["up"][up], ops.act(glo))
+            names = [f"{pre}{up}.weight", f"{pre}{up}.bias"]
+            # the gradient slots are allocated on the launch stream (their consumers run there)
+            dw, db = sink.slot(names[0], (C, C, 2, 2)), sink.slot(names[1], (C,))
+
+            def wgrad():
+                ya = ops.act(s["yb"])
+                ns = ops.upconv2x2_wgrad_splits(ya, dt)
+                dwp = _e(ns * 4 * C * C, torch.float32, dev)
+                dbp = _e(ns * 4 * C, torch.float32, dev)
+                ops.upconv2x2_wgrad(ya, s["bnb"]["scale"], s["bnb"]["shift"], ghi, dwp, dbp, ns)
+                ops.wgrad_reduce(dwp, None, ns, C, C, 4, dw, None)  # [ci][2a+b][co] partials -> torch [ci][co][2][2]
+                ops.colsum(dbp, ns * 4, C, db)
+                sink.ready(names)
+
+            if not self.overlap_wgrad:
+                wgrad()
+                return None, 0
+            main, side = torch.cuda.current_stream(dev), side_stream(dev)
+            self._wait(side, main)  # the concat gradient (and everything before it) is ready
+            with torch.cuda.stream(side):
+                wgrad()
+            for t in (ghi._keep, s["yb"], dw, db):  # the caching allocator must not hand these out early
+                t.record_stream(side)
+            return None, 0
+
+        def up_bwd(ghi: ops.Act, glo: torch.Tensor, nm, up):
             """g w.r.t. block nm's output from the upsample adjoint, its BN-b reduction fused."""
+            if self.transpose:
+                return upconv_bwd(ghi, glo, nm, up)
             rows = ops.upsample_bwd_bnr_rows(ops.act(glo))
             if not rows:
                 ops.upsample_bwd(ghi, ops.act(glo))
@@ -485,15 +530,15 @@ class UNetEngine:
         g_cat2 = self._block_bwd("dec2", gd2, S, P, sink, need_gx=True, small=False, gred=red2)
         del gd2
         g_d3 = _e((N, H >> 1, W >> 1, ch[1]), dt, dev)
-        red = up_bwd(ops.act(g_cat2, 0, ch[1]), g_d3, "dec3")
+        red = up_bwd(ops.act(g_cat2, 0, ch[1]), g_d3, "dec3", "up2")
         g_cat3 = self._block_bwd("dec3", g_d3, S, P, sink, need_gx=True, small=False, gred=red)
         del g_d3
         g_d4 = _e((N, H >> 2, W >> 2, ch[2]), dt, dev)
-        red = up_bwd(ops.act(g_cat3, 0, ch[2]), g_d4, "dec4")
+        red = up_bwd(ops.act(g_cat3, 0, ch[2]), g_d4, "dec4", "up3")
         g_cat4 = self._block_bwd("dec4", g_d4, S, P, sink, need_gx=True, small=False, gred=red)
         del g_d4
         g_e4 = _e((N, H >> 3, W >> 3, ch[3]), dt, dev)
-        red = up_bwd(ops.act(g_cat4, 0, ch[3]), g_e4, "enc4")
+        red = up_bwd(ops.act(g_cat4, 0, ch[3]), g_e4, "enc4", "up4")
         # ---- encoder (skip gradients + max-pool backward)
         g_p3 = self._block_bwd("enc4", g_e4, S, P, sink, need_gx=True, small=False, gred=red)
         del g_e4

@@ -13,7 +13,8 @@ is not importable, models.py:71-76, 304-314):
 
 Build-side keyword-only generalisations (BASELINE configs): in_channels,
 base_ch, dtype ('fp32' | 'bf16' compute/storage of activations; parameters,
-BN statistics and the loss stay fp32).
+BN statistics and the loss stay fp32), and upsample ('bilinear' | 'transpose':
+how the decoder's three trunk upsamples are made, see _UNetParams).
 
 The nn layers below are parameter containers only (their initialisation and
 state_dict naming match the reference); forward never runs them -- it runs the
@@ -37,10 +38,21 @@ def _double_conv(cin: int, cout: int) -> nn.Sequential:
                          nn.Conv2d(cout, cout, 3, padding=1), nn.BatchNorm2d(cout), nn.ReLU(inplace=True))
 
 
-class _UNetParams(nn.Module):
-    """Parameter tree of BasicUNet (models.py:199-215)."""
+UPSAMPLES = ("bilinear", "transpose")
 
-    def __init__(self, in_channels: int, base_ch: int, num_classes: int):
+
+class _UNetParams(nn.Module):
+    """Parameter tree of BasicUNet (models.py:199-215).
+
+    upsample="transpose" (no reference counterpart; BASELINE.json north_star's "bilinear/transposed-conv
+    upsample") adds up4 / up3 / up2 after dec1: channel-preserving ConvTranspose2d(C, C, 2, stride=2) with
+    bias at C = 8b, 4b, 2b, which replace the bilinear upsamples enc4 -> dec4, dec4 -> dec3 and dec3 -> dec2
+    (the concat buffers and every dec*.0 weight shape stay as they are).  The LAST upsample -- the 2x one
+    behind dec2, commuted behind dec1 into the head / ktail kernels as a K-channel fp32 operation -- stays
+    bilinear in either mode: dec1(up(d2)) = up(dec1(d2)) holds only for a per-channel linear upsample, which
+    a learned transposed convolution is not."""
+
+    def __init__(self, in_channels: int, base_ch: int, num_classes: int, upsample: str = "bilinear"):
         super().__init__()
         b = base_ch
         self.enc1 = _double_conv(in_channels, b)
@@ -51,6 +63,32 @@ class _UNetParams(nn.Module):
         self.dec3 = _double_conv(4 * b + 2 * b, 2 * b)
         self.dec2 = _double_conv(2 * b + b, b)
         self.dec1 = nn.Conv2d(b, num_classes, 1)
+        if upsample == "transpose":
+            self.up4 = nn.ConvTranspose2d(8 * b, 8 * b, 2, stride=2)
+            self.up3 = nn.ConvTranspose2d(4 * b, 4 * b, 2, stride=2)
+            self.up2 = nn.ConvTranspose2d(2 * b, 2 * b, 2, stride=2)
+
+
+def _check_upsample(upsample: str):
+    if upsample not in UPSAMPLES:
+        raise ValueError(f"upsample must be one of {UPSAMPLES}, got {upsample!r}")
+
+
+def _transpose_backward_order(model):
+    """Gradient-production order of a transpose-upsample model (eunet.dp buckets): eunet.dp's default order
+    with each up* layer behind the decoder block whose input gradient feeds it -- enhance (EnhancedUNet only),
+    dec1, dec2, up2, dec3, up3, dec4, up4, enc4 ... enc1; inside a block: .4, .3, .1, .0 (engine._block_bwd)."""
+    names = [n for n, _ in model.named_parameters()]
+    order = [n for n in names if n.startswith("enhance.")]
+    order += [n for n in names if n.startswith("model.dec1.")]
+    for blk in ("dec2", "up2", "dec3", "up3", "dec4", "up4", "enc4", "enc3", "enc2", "enc1"):
+        pre = f"model.{blk}."
+        blk_names = [n for n in names if n.startswith(pre)]
+        if not blk.startswith("up"):
+            blk_names.sort(key=lambda n: {"4": 0, "3": 1, "1": 2, "0": 3}[n[len(pre)]])
+        order += blk_names
+    assert sorted(order) == sorted(names), "backward order must cover every parameter"
+    return order
 
 
 def _check_limits(num_classes: int, in_channels: int, base_ch: int):
@@ -97,13 +135,22 @@ class UNet(_EngineModel):
     """Reference UNet wrapper (models.py:175-243), SMP-absent: holds BasicUNet as .model; the
     Enhanced-UNet trunk without the enhance head, on the same engine."""
 
-    def __init__(self, num_classes: int = 3, *, in_channels: int = 3, base_ch: int = 64, dtype: str = "fp32"):
+    def __init__(self, num_classes: int = 3, *, in_channels: int = 3, base_ch: int = 64, dtype: str = "fp32",
+                 upsample: str = "bilinear"):
+        """upsample: 'bilinear' (the reference) or 'transpose' (learned 2x2 up-convolutions for the three trunk
+        upsamples, _UNetParams; the final 2x upsample behind dec1 stays bilinear).  A bilinear checkpoint
+        loads into a transpose model with strict=False (up* keep their initialisation); strict=True fails on
+        the six missing up* keys."""
         super().__init__()
+        _check_upsample(upsample)
         self._setup(num_classes, in_channels, base_ch, dtype)
-        self.model = _UNetParams(in_channels, base_ch, num_classes)
+        self.upsample = upsample
+        self.model = _UNetParams(in_channels, base_ch, num_classes, upsample)
         self._engine = PlainUNetEngine(self)
 
     def backward_param_order(self):
+        if self.upsample == "transpose":
+            return _transpose_backward_order(self)
         return None  # eunet.dp's default order (dec1, dec2 ... enc1) is this engine's
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -120,8 +167,16 @@ class EnhancedUNet(nn.Module):
     """Enhanced U-Net (reference fallback definition) on the MI355X engine."""
 
     def __init__(self, num_classes: int = 3, *, in_channels: int = 3, base_ch: int = 64, dtype: str = "fp32",
-                 dual_branch: bool = False):
+                 dual_branch: bool = False, upsample: str = "bilinear"):
+        """upsample: 'bilinear' (the reference) or 'transpose' (learned 2x2 up-convolutions for the three trunk
+        upsamples, _UNetParams; the final 2x upsample, fused into the head kernels behind dec1, stays
+        bilinear).  A bilinear checkpoint loads into a transpose model with strict=False (up* keep their
+        initialisation); strict=True fails on the six missing up* keys.  Not built for dual_branch."""
         super().__init__()
+        _check_upsample(upsample)
+        if dual_branch and upsample != "bilinear":
+            raise ValueError("upsample='transpose' is not built for the dual-branch model")
+        self.upsample = upsample
         if not 1 <= num_classes <= 3:
             raise ValueError("num_classes must be 1..3 (the reference loss tables have 3 classes)")
         if in_channels > 4:
@@ -152,7 +207,7 @@ class EnhancedUNet(nn.Module):
             self.fusion_residual = nn.Conv2d(k2, num_classes, 1)
             self._engine = DualEngine(self)
         else:  # SMP-absent fallback (models.py:304-314)
-            self.model = UNet(num_classes, in_channels=in_channels, base_ch=base_ch).model
+            self.model = UNet(num_classes, in_channels=in_channels, base_ch=base_ch, upsample=upsample).model
             self.enhance = nn.Sequential(nn.Conv2d(num_classes, 64, 3, padding=1), nn.BatchNorm2d(64),
                                          nn.ReLU(inplace=True), nn.Conv2d(64, num_classes, 1))
             self._engine = UNetEngine(self)
@@ -164,7 +219,9 @@ class EnhancedUNet(nn.Module):
 
     def backward_param_order(self):
         """Parameter names in gradient-production order (eunet.dp buckets)."""
-        return dual_backward_order(self) if self.dual_branch else None
+        if self.dual_branch:
+            return dual_backward_order(self)
+        return _transpose_backward_order(self) if self.upsample == "transpose" else None
 
     def _run_dual(self, x: torch.Tensor) -> torch.Tensor:
         """models.py:317-333: fused logits [B,K,H,W]; _aux_outputs = branch logits."""
@@ -208,7 +265,7 @@ def get_model(model_name: str, num_classes: int = 3, device: str = "cuda", train
     """models.py:590-624.  Built here: 'enhanced_unet', and the baseline made of the same ops, 'unet'
     (BasicUNet: the Enhanced-UNet trunk without the enhance head).  The other reference nets ('segnet',
     'fcn', 'pspnet', 'linknet') are not built and raise like unknown names.  kwargs: the
-    build's keywords (in_channels, base_ch, dtype)."""
+    build's keywords (in_channels, base_ch, dtype, upsample)."""
     if model_name == "enhanced_unet":
         return EnhancedUNet(num_classes=num_classes, **kwargs)
     if model_name == "unet":

@@ -485,6 +485,91 @@ def upsample_bwd_bnr(ghi: Act, glo: Act, y: Act, mean, invstd, scale, shift, par
          _ptr(scale), _ptr(shift), _ptr(part), _stream())
 
 
+# ---- learned 2x upsample: ConvTranspose2d(C, C, 2, stride=2) behind a BN+ReLU (upconv.hip) ----------
+# kprof family "upconv2x2", credited with the algorithmic counts of one pass: 8 M C^2 FLOP and, in bytes,
+# the M x C low-res tensor + the 4M x C high-res one + the weights (10 M C at bf16).
+def _upconv_counts(lo: Act, extra_bytes: float = 0.0):
+    m = lo.n * lo.h * lo.w
+    esz = 2 if lo.dtype == _lib.EUNET_BF16 else 4
+    return 8.0 * m * lo.c * lo.c, float(esz * (5 * m * lo.c + 4 * lo.c * lo.c)) + extra_bytes
+
+
+def upconv2x2_packed_bytes(c, dtype):
+    b = c_size_t()
+    call("eunet_upconv2x2_packed_bytes", c, DTYPES[dtype], ctypes.byref(b))
+    return b.value
+
+
+def _upconv_weight(name, w):
+    if w.dim() != 4 or w.shape[0] != w.shape[1] or tuple(w.shape[2:]) != (2, 2) or w.dtype != torch.float32:
+        raise _lib.EunetError(f"{name}: need an fp32 ConvTranspose2d weight [C, C, 2, 2], got {w.dtype} {tuple(w.shape)}")
+    return w.shape[0]
+
+
+@_dispatched("T d", returns_tensor=True)
+def upconv2x2_pack(w: torch.Tensor, dtype) -> torch.Tensor:
+    """torch weight [C, C, 2, 2] fp32 -> the packed forward + data-gradient operands (once per step)."""
+    c = _upconv_weight("upconv2x2_pack", w)
+    if dtype not in DTYPES:
+        raise _lib.EunetError(f"upconv2x2_pack: dtype {dtype} is not fp32 / bf16")
+    wp = torch.empty(8 * c * c, dtype=dtype, device=w.device)
+    with kprof.timed("upconv2x2", 0.0, float(16 * c * c + wp.numel() * wp.element_size())):
+        call("eunet_upconv2x2_pack", _ptr(w.contiguous()), c, _ptr(wp), DTYPES[dtype], _stream())
+    return wp
+
+
+def _upconv_packed(name, wp, a: Act):
+    if wp.dim() != 1 or DTYPES.get(wp.dtype) != a.dtype or wp.numel() != 8 * a.c * a.c:
+        raise _lib.EunetError(f"{name}: packed weights {wp.dtype} [{wp.numel()}] do not fit C = {a.c} of the "
+                              "activations (upconv2x2_pack of the same dtype)")
+
+
+@_dispatched("A T T T T A!")
+def bnrelu_upconv2x2(y: Act, scale, shift, wp, bias, out: Act):
+    """out[n, 2i+a, 2j+b, :] = bias + relu(bn(y))[n, i, j, :] @ W[:, :, a, b] (eunet_bnrelu_upconv2x2_fwd)."""
+    _upconv_packed("bnrelu_upconv2x2", wp, y)
+    for nm, t in (("scale", scale), ("shift", shift), ("bias", bias)):
+        if t.dtype != torch.float32 or t.numel() != y.c:
+            raise _lib.EunetError(f"bnrelu_upconv2x2: {nm} must be fp32 [{y.c}], got {t.dtype} {tuple(t.shape)}")
+    flops, nbytes = _upconv_counts(y)
+    with kprof.timed("upconv2x2", flops, nbytes):
+        call("eunet_bnrelu_upconv2x2_fwd", ctypes.byref(y), _ptr(scale), _ptr(shift), _ptr(wp), _ptr(bias),
+             ctypes.byref(out), _stream())
+
+
+@_dispatched("A T A!")
+def upconv2x2_dgrad(g: Act, wp, gd: Act):
+    """gd[n, i, j, ci] = sum_{a, b, co} g[n, 2i+a, 2j+b, co] W[ci, co, a, b]: the gradient w.r.t. relu(bn(y))."""
+    _upconv_packed("upconv2x2_dgrad", wp, gd)
+    flops, nbytes = _upconv_counts(gd)
+    with kprof.timed("upconv2x2", flops, nbytes):
+        call("eunet_upconv2x2_dgrad", ctypes.byref(g), _ptr(wp), ctypes.byref(gd), _stream())
+
+
+def upconv2x2_wgrad_splits(y: Act, dtype) -> int:
+    s = c_int()
+    call("eunet_upconv2x2_wgrad_splits", ctypes.byref(y), DTYPES[dtype], ctypes.byref(s))
+    return s.value
+
+
+@_dispatched("A T T A T! T!? i")
+def upconv2x2_wgrad(y: Act, scale, shift, g: Act, dw_part, db_part, nsplit):
+    """Split partials of dW and db: dw_part [nsplit, C, 4, C] (wgrad_reduce(cout = cin = C, taps = 4) -> torch's
+    [C, C, 2, 2]), db_part [nsplit, 4, C] (colsum over nsplit * 4 rows -> db)."""
+    c = y.c
+    if dw_part.dtype != torch.float32 or dw_part.numel() < nsplit * 4 * c * c:
+        raise _lib.EunetError(f"upconv2x2_wgrad: dw_part must be fp32 with >= {nsplit * 4 * c * c} elements")
+    if db_part is not None and (db_part.dtype != torch.float32 or db_part.numel() < nsplit * 4 * c):
+        raise _lib.EunetError(f"upconv2x2_wgrad: db_part must be fp32 with >= {nsplit * 4 * c} elements")
+    for nm, t in (("scale", scale), ("shift", shift)):
+        if t.dtype != torch.float32 or t.numel() != c:
+            raise _lib.EunetError(f"upconv2x2_wgrad: {nm} must be fp32 [{c}], got {t.dtype} {tuple(t.shape)}")
+    flops, nbytes = _upconv_counts(y, 4.0 * nsplit * 4 * c * (c + 1))
+    with kprof.timed("upconv2x2", flops, nbytes):
+        call("eunet_upconv2x2_wgrad", ctypes.byref(y), _ptr(scale), _ptr(shift), ctypes.byref(g), _ptr(dw_part),
+             _ptr(db_part), int(nsplit), _stream())
+
+
 def conv1x1_bwd_tiles(y: Act) -> int:
     t = c_int()
     call("eunet_conv1x1_bwd_tiles", ctypes.byref(y), ctypes.byref(t))

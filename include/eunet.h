@@ -159,6 +159,32 @@ int eunet_bnrelu_pool(const eunet_act* y, const float* scale, const float* shift
 /* Upsample x2 bilinear, align_corners=False (models.py:215, 233-236) */
 int eunet_bnrelu_upsample(const eunet_act* y, const float* scale, const float* shift,
                           const eunet_act* out, void* stream);
+/* ---- learned decoder upsample: ConvTranspose2d(C, C, kernel_size=2, stride=2) ------------------------
+ * No reference line to cite: the reference has no transposed convolution.  The source is the project's
+ * own statement of purpose, BASELINE.json north_star ("bilinear/transposed-conv upsample"); the model
+ * keyword upsample="transpose" puts this layer where eunet_bnrelu_upsample stands (the three trunk
+ * upsamples; the last, K-channel one inside the head / ktail kernels stays bilinear).
+ *   d  = relu(fmaf(y, scale, shift))                  (rounded to the compute dtype)
+ *   up[n, 2i+a, 2j+b, co] = bias[co] + sum_ci d[n,i,j,ci] * W[ci,co,a,b]       a, b in {0, 1}
+ * y: the producing block's pre-BN conv output, scale / shift its BN affine; W the torch parameter
+ * [C][C][2][2] fp32.  C must be a multiple of 32 and the 2x view has y's n, 2h, 2w and c (anything
+ * else: EUNET_ERR_INVALID); views honour ctot / coff.  MFMA kernels for both dtypes.
+ * pack: W -> wp (eunet_upconv2x2_packed_bytes bytes, the compute dtype): the forward's [4C][C] image
+ * followed by the data gradient's [C][4C] one; once per step. */
+int eunet_upconv2x2_packed_bytes(int c, int dtype, size_t* bytes);
+int eunet_upconv2x2_pack(const float* w, int c, void* wp, int dtype, void* stream);
+int eunet_bnrelu_upconv2x2_fwd(const eunet_act* y, const float* scale, const float* shift, const void* wp,
+                               const float* bias, const eunet_act* out, void* stream);
+/* gd[n,i,j,ci] = sum_{a,b,co} g[n,2i+a,2j+b,co] * W[ci,co,a,b]: the gradient w.r.t. d (the post-ReLU
+ * activation; the block's BN backward applies the ReLU mask from y: eunet_bn_bwd_reduce / _apply) */
+int eunet_upconv2x2_dgrad(const eunet_act* g, const void* wp, const eunet_act* gd, void* stream);
+/* dW[ci,co,a,b] = sum_{n,i,j} d * g and db[co] = sum g, split over pixel tiles (y: the low-res view):
+ * dw_part [nsplit][C][4][C] = [ci][2a+b][co] (eunet_wgrad_reduce(cout = cin = C, taps = 4) gives torch's
+ * [ci][co][2][2]) and db_part (nullable) [nsplit][4][C] (eunet_colsum over its nsplit * 4 rows gives
+ * db); fixed summation order, no atomics: two runs are bit-identical */
+int eunet_upconv2x2_wgrad_splits(const eunet_act* y, int dtype, int* nsplit);
+int eunet_upconv2x2_wgrad(const eunet_act* y, const float* scale, const float* shift, const eunet_act* g,
+                          float* dw_part, float* db_part, int nsplit, void* stream);
 /* dec1 1x1 conv (models.py:212,236), commuted before the upsample:
  * z[p][k] = b[k] + sum_c w[k][c] * relu(bn(y))[p][c]; z fp32 NHWC [N,H,W,K] */
 int eunet_bnrelu_conv1x1(const eunet_act* y, const float* scale, const float* shift,
@@ -267,7 +293,7 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
  * eunet_debug_enabled: 1 in the debug build, 0 in the release library (where the checks compile away).
  * eunet_debug_status: synchronises the device; *count = failed checks since the last reset,
  * *unit_line = unit * 100000 + source line of the first (units: 1 capi, 2 conv3x3, 3 bn_pool_up,
- * 4 head, 5 instances, 6 baselines; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
+ * 4 head, 5 instances, 6 baselines, 7 upconv; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
 int eunet_debug_enabled(void);
 int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset);
 int eunet_debug_selftest(void* stream);
