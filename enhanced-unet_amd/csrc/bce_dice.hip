@@ -1,0 +1,443 @@
+// Sigmoid BCE + soft Dice loss for binary and multi-label training, fused and batched, and the
+// sigmoid prediction path of the evaluator.
+//
+// No reference line to cite: the reference has no BCE.  The source is the
+// project's own statement of purpose, BASELINE.json north_star ("BCE/Dice" per-pixel loss); the
+// definition is the one in include/eunet.h (eunet_bce_dice_fwd):
+//   sp(z)  = max(z, 0) + log1p(exp(-|z|)),  sig = sigmoid
+//   bce_c  = cw_c (pw_c t_c sp(-x_c) + (1 - t_c) sp(x_c))     (F.binary_cross_entropy_with_logits)
+//   BCE    = sum_{n,c,valid px} bce / (K max(1, V)),  V = number of valid pixels of the batch
+//   dice_n = (1/K) sum_c dw_c (1 - (2 I + s)/(S + T + s)),  I = sum sig t, S = sum sig, T = sum t
+//   loss   = w_bce BCE + w_dice (1/N) sum_n dice_n
+// t_c = [target == c] (onehot) or t_0 = [target >= 1] (foreground, K = 1).  A pixel at ignore_index
+// contributes to nothing -- not to the BCE sum, its denominator, I, S or T.  (loss.hip differs: there
+// an ignored pixel's probability still counts in S.)  A pixel that is neither valid nor ignored
+// contributes nothing either and is counted into the last element of sums, where eunet_loss_fwd
+// puts its count.
+//
+// Three HBM-bound streams.  Forward: one block per (sample, tile of 1024 pixels) reads the logits and
+// the target once (16 bytes per lane when H*W is a multiple of 4), reduces in the wave and writes one
+// partial row; a single block sums the partials in fp64 in a fixed order (deterministic).  Backward:
+// analytic per pixel from the saved sums, logits and target read once, the gradient written once.
+#include "common.h"
+
+EUNET_DEBUG_UNIT(bcedice)
+
+namespace {
+constexpr int NT = 256;
+constexpr int LPIX = 1024;  // pixels per partial tile: 4 per thread
+
+const eunet_bce_dice_params kDefaultParams = {
+    {1.f, 1.f, 1.f}, {1.f, 1.f, 1.f}, {1.f, 1.f, 1.f}, 1.f, 1.f, 1e-6f, EUNET_NO_IGNORE, EUNET_BCE_TARGET_AUTO};
+
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+
+// sig(x), sig(-x), sp(x), sp(-x) from one exp: no overflow and no cancellation at +-100
+struct Sig {
+  float p, q, spp, spn;
+};
+template <bool WITH_SP>
+__device__ __forceinline__ Sig sigmoid_terms(float x) {
+  const float e = expf(-fabsf(x));
+  const float r = 1.f / (1.f + e);
+  const float hi = r, lo = e * r;
+  Sig s;
+  s.p = x >= 0.f ? hi : lo;
+  s.q = x >= 0.f ? lo : hi;
+  if (WITH_SP) {
+    const float l = log1pf(e);
+    s.spp = fmaxf(x, 0.f) + l;
+    s.spn = fmaxf(-x, 0.f) + l;
+  } else {
+    s.spp = s.spn = 0.f;
+  }
+  return s;
+}
+
+// 0 ignored, 1 valid, 2 out of range
+__device__ __forceinline__ int classify(int64_t traw, int K, const eunet_bce_dice_params& prm) {
+  if (traw == (int64_t)prm.ignore_index) return 0;
+  const bool ok = prm.target_mode == EUNET_BCE_TARGET_FOREGROUND ? traw >= 0 : (traw >= 0 && traw < K);
+  return ok ? 1 : 2;
+}
+
+__device__ __forceinline__ float target_of(int64_t traw, int c, const eunet_bce_dice_params& prm) {
+  const bool on = prm.target_mode == EUNET_BCE_TARGET_FOREGROUND ? traw >= 1 : traw == (int64_t)c;
+  return on ? 1.f : 0.f;
+}
+
+// acc: [0] bce sum, [1+c] I, [1+K+c] S, [1+2K+c] T, [1+3K] valid pixels, [2+3K] out-of-range targets
+template <int K>
+__device__ __forceinline__ void fwd_px(const float (&x)[K], int64_t traw, const eunet_bce_dice_params& prm,
+                                       float (&acc)[3 + 3 * K]) {
+  const int cls = classify(traw, K, prm);
+  if (cls == 2) acc[2 + 3 * K] += 1.f;
+  if (cls != 1) return;
+  acc[1 + 3 * K] += 1.f;
+#pragma unroll
+  for (int c = 0; c < K; ++c) {
+    const Sig s = sigmoid_terms<true>(x[c]);
+    const float t = target_of(traw, c, prm);
+    acc[0] += prm.class_weight[c] * (prm.pos_weight[c] * t * s.spn + (1.f - t) * s.spp);
+    acc[1 + c] += s.p * t;
+    acc[1 + K + c] += s.p;
+    acc[1 + 2 * K + c] += t;
+  }
+}
+
+template <int K, bool VEC>
+__global__ __launch_bounds__(NT) void bce_dice_fwd_kernel(const float* logits, const int64_t* target, int HW,
+                                                          eunet_bce_dice_params prm, float* part) {
+  constexpr int NV = 3 + 3 * K;
+  __shared__ float red[4][NV];
+  const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const float* lg = logits + (long long)n * K * HW;
+  const int64_t* tg = target + (long long)n * HW;
+  float acc[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) acc[i] = 0.f;
+  const int p0 = blockIdx.x * LPIX;
+  const int p1 = min(HW, p0 + LPIX);
+  if (VEC) {  // HW % 4 == 0: every plane and every 4-pixel group starts on 16 bytes
+    const int p = p0 + tid * 4;
+    if (p < p1) {
+      EUNET_DASSERT(p + 3 < HW);
+      f32x4 xv[K];
+#pragma unroll
+      for (int c = 0; c < K; ++c) xv[c] = *reinterpret_cast<const f32x4*>(lg + (long long)c * HW + p);
+      const i64x2 t01 = *reinterpret_cast<const i64x2*>(tg + p);
+      const i64x2 t23 = *reinterpret_cast<const i64x2*>(tg + p + 2);
+      const int64_t tr[4] = {t01[0], t01[1], t23[0], t23[1]};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float x[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c) x[c] = xv[c][j];
+        fwd_px<K>(x, tr[j], prm, acc);
+      }
+    }
+  } else {
+    for (int p = p0 + tid; p < p1; p += NT) {
+      EUNET_DASSERT(p < HW);
+      float x[K];
+#pragma unroll
+      for (int c = 0; c < K; ++c) x[c] = lg[(long long)c * HW + p];
+      fwd_px<K>(x, tg[p], prm, acc);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const float s = wave_sum(acc[i]);
+    if (lane == 0) red[wv][i] = s;
+  }
+  __syncthreads();
+  if (tid < NV)
+    part[((long long)n * gridDim.x + blockIdx.x) * NV + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+}
+
+// One 256-thread block: per sample, the threads stride over the tile partials (fp64), a fixed-order
+// LDS tree combines them (deterministic), thread 0 forms the sample's terms; the batch sums are
+// taken in sample order.
+template <int K>
+__global__ __launch_bounds__(256) void bce_dice_finalize_kernel(const float* part, int tiles, int N,
+                                                                eunet_bce_dice_params prm, float* sums,
+                                                                float* loss, float* parts) {
+  constexpr int NV = 3 + 3 * K;
+  __shared__ double red[256][NV];
+  __shared__ double dice_s[64], bnum[64], vcnt[64], nbad[64];
+  const int tid = threadIdx.x;
+  EUNET_DASSERT(N <= 64);
+  for (int n = 0; n < N; ++n) {
+    double v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = 0.0;
+    for (int t = tid; t < tiles; t += 256)
+#pragma unroll
+      for (int i = 0; i < NV; ++i) v[i] += (double)part[((long long)n * tiles + t) * NV + i];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) red[tid][i] = v[i];
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+      if (tid < off)
+#pragma unroll
+        for (int i = 0; i < NV; ++i) red[tid][i] += red[tid + off][i];
+      __syncthreads();
+    }
+    if (tid == 0) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        v[i] = red[0][i];
+        sums[n * NV + i] = (float)v[i];
+      }
+      const double sm = (double)prm.smooth;
+      double dice = 0.0;
+      for (int c = 0; c < K; ++c) {
+        const double I = v[1 + c], S = v[1 + K + c], T = v[1 + 2 * K + c];
+        dice += prm.dice_weight[c] * (1.0 - (2.0 * I + sm) / (S + T + sm));
+      }
+      dice /= (double)K;
+      const double vn = v[1 + 3 * K];
+      if (parts) {
+        parts[n * 2 + 0] = (float)(v[0] / ((double)K * (vn > 1.0 ? vn : 1.0)));
+        parts[n * 2 + 1] = (float)dice;
+      }
+      dice_s[n] = dice;
+      bnum[n] = v[0];
+      vcnt[n] = vn;
+      nbad[n] = v[2 + 3 * K];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double d = 0.0, b = 0.0, vt = 0.0, nb = 0.0;
+    for (int i = 0; i < N; ++i) {
+      d += dice_s[i];
+      b += bnum[i];
+      vt += vcnt[i];
+      nb += nbad[i];
+    }
+    const double bce = b / ((double)K * (vt > 1.0 ? vt : 1.0));  // no valid pixel: b = 0, the loss is 0
+    loss[0] = (float)(prm.w_bce * bce + prm.w_dice * d / (double)N);
+    sums[N * NV] = (float)vt;
+    sums[N * NV + 1] = (float)nb;
+  }
+}
+
+// per (sample, class): the Dice gradient is (a t + b) sig(x) sig(-x)
+template <int K>
+struct DiceCoef {
+  float a[K], b[K];
+};
+template <int K>
+__device__ __forceinline__ DiceCoef<K> dice_coef(const float* sm, int N, const eunet_bce_dice_params& prm) {
+  DiceCoef<K> d;
+#pragma unroll
+  for (int c = 0; c < K; ++c) {
+    const float I = sm[1 + c], S = sm[1 + K + c], T = sm[1 + 2 * K + c];
+    const float u = S + T + prm.smooth;
+    const float w = prm.w_dice * prm.dice_weight[c] / (float)(N * K);
+    d.a[c] = -2.f * w / u;
+    d.b[c] = w * (2.f * I + prm.smooth) / (u * u);
+  }
+  return d;
+}
+
+template <int K>
+__device__ __forceinline__ void bwd_px(const float (&x)[K], int64_t traw, const eunet_bce_dice_params& prm,
+                                       const DiceCoef<K>& dc, float cb, float g0, float (&g)[K]) {
+  const bool valid = classify(traw, K, prm) == 1;
+#pragma unroll
+  for (int c = 0; c < K; ++c) {
+    const Sig s = sigmoid_terms<false>(x[c]);
+    const float t = target_of(traw, c, prm);
+    const float gb = cb * prm.class_weight[c] * (-prm.pos_weight[c] * t * s.q + (1.f - t) * s.p);
+    const float gd = (dc.a[c] * t + dc.b[c]) * s.p * s.q;
+    g[c] = valid ? g0 * (gb + gd) : 0.f;
+  }
+}
+
+// VEC: one thread per group of 4 pixels (HW % 4 == 0, so a group never straddles two samples)
+template <int K, bool VEC>
+__global__ __launch_bounds__(NT) void bce_dice_bwd_kernel(const float* logits, const int64_t* target, int N, int HW,
+                                                          eunet_bce_dice_params prm, const float* sums,
+                                                          const float* gloss, float* glog) {
+  constexpr int NV = 3 + 3 * K;
+  constexpr int PER = VEC ? 4 : 1;
+  const long long id = ((long long)blockIdx.x * NT + threadIdx.x) * PER;
+  const long long total = (long long)N * HW;
+  if (id >= total) return;
+  EUNET_DASSERT(id + PER <= total);
+  const int n = (int)(id / HW);
+  const int p = (int)(id - (long long)n * HW);
+  EUNET_DASSERT(n < N && p + PER <= HW);
+  const float* lg = logits + (long long)n * K * HW + p;
+  float* gl = glog + (long long)n * K * HW + p;
+  const DiceCoef<K> dc = dice_coef<K>(sums + n * NV, N, prm);
+  const float vt = sums[N * NV];
+  const float cb = prm.w_bce / ((float)K * fmaxf(vt, 1.f));
+  const float g0 = gloss[0];
+  if (VEC) {
+    f32x4 xv[K], gv[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) xv[c] = *reinterpret_cast<const f32x4*>(lg + (long long)c * HW);
+    const i64x2 t01 = *reinterpret_cast<const i64x2*>(target + id);
+    const i64x2 t23 = *reinterpret_cast<const i64x2*>(target + id + 2);
+    const int64_t tr[4] = {t01[0], t01[1], t23[0], t23[1]};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float x[K], g[K];
+#pragma unroll
+      for (int c = 0; c < K; ++c) x[c] = xv[c][j];
+      bwd_px<K>(x, tr[j], prm, dc, cb, g0, g);
+#pragma unroll
+      for (int c = 0; c < K; ++c) gv[c][j] = g[c];
+    }
+#pragma unroll
+    for (int c = 0; c < K; ++c) *reinterpret_cast<f32x4*>(gl + (long long)c * HW) = gv[c];
+  } else {
+    float x[K], g[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) x[c] = lg[(long long)c * HW];
+    bwd_px<K>(x, target[id], prm, dc, cb, g0, g);
+#pragma unroll
+    for (int c = 0; c < K; ++c) gl[(long long)c * HW] = g[c];
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(NT) void sigmoid_crop_kernel(const float* logits, int hp, int wp, int h, int w,
+                                                          int flip_h, int flip_w, float* probs) {
+  const long long total = (long long)h * w;
+  for (long long id = (long long)blockIdx.x * NT + threadIdx.x; id < total; id += (long long)gridDim.x * NT) {
+    const int x = (int)(id % w), yy = (int)(id / w);
+    const int sy = flip_h ? h - 1 - yy : yy, sx = flip_w ? w - 1 - x : x;
+    EUNET_DASSERT(sy >= 0 && sy < hp && sx >= 0 && sx < wp);
+    const long long s = (long long)sy * wp + sx;
+#pragma unroll
+    for (int k = 0; k < K; ++k) probs[(long long)k * total + id] = sigmoid_terms<false>(logits[(long long)k * hp * wp + s]).p;
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(NT) void probs_threshold_kernel(const float* probs, long long hw, float thr,
+                                                             int64_t* mask) {
+  for (long long id = (long long)blockIdx.x * NT + threadIdx.x; id < hw; id += (long long)gridDim.x * NT) {
+    int64_t m;
+    if (K == 1) {
+      m = probs[id] >= thr ? 1 : 0;
+    } else {
+      float best = probs[id];
+      m = 0;
+#pragma unroll
+      for (int k = 1; k < K; ++k) {
+        const float v = probs[(long long)k * hw + id];
+        if (v > best) {  // strict: the first maximum wins a tie
+          best = v;
+          m = k;
+        }
+      }
+    }
+    mask[id] = m;
+  }
+}
+
+inline unsigned grid_for(long long n) {
+  const long long b = (n + NT - 1) / NT;
+  return (unsigned)(b < 2048 ? (b > 0 ? b : 1) : 2048);
+}
+
+// the params of a call with target_mode resolved for K; false (error set) when they are refused
+bool resolve(const eunet_bce_dice_params* params, int k, eunet_bce_dice_params* out, const char* what) {
+  *out = params ? *params : kDefaultParams;
+  if (out->target_mode == EUNET_BCE_TARGET_AUTO)
+    out->target_mode = k == 1 ? EUNET_BCE_TARGET_FOREGROUND : EUNET_BCE_TARGET_ONEHOT;
+  if (out->target_mode == EUNET_BCE_TARGET_FOREGROUND ? k != 1 : (out->target_mode != EUNET_BCE_TARGET_ONEHOT || k == 1)) {
+    eunet::set_error("%s: target_mode %d with K = %d (foreground is the mode of K = 1, and its only one)", what,
+                     out->target_mode, k);
+    return false;
+  }
+  if (!(out->smooth > 0.f)) {
+    eunet::set_error("%s: smooth must be > 0", what);
+    return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int eunet_bce_dice_default_params(eunet_bce_dice_params* prm) {
+  EUNET_REQUIRE(prm, "bce_dice_default_params: null");
+  *prm = kDefaultParams;
+  return EUNET_OK;
+}
+
+int eunet_bce_dice_sums_len(int n, int k, int* len) {
+  EUNET_REQUIRE(len && n > 0 && k >= 1 && k <= 3, "bce_dice_sums_len: bad args");
+  *len = n * (3 + 3 * k) + 2;
+  return EUNET_OK;
+}
+
+int eunet_bce_dice_workspace_bytes(int n, int k, int h, int w, size_t* bytes) {
+  EUNET_REQUIRE(bytes && n > 0 && k >= 1 && k <= 3 && h > 0 && w > 0, "bce_dice_workspace_bytes: bad args");
+  const int tiles = cdiv(h * w, LPIX);
+  *bytes = (size_t)n * tiles * (3 + 3 * k) * sizeof(float);
+  return EUNET_OK;
+}
+
+int eunet_bce_dice_fwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
+                       const eunet_bce_dice_params* params, float* sums, float* loss, float* parts, void* ws,
+                       void* stream) {
+  EUNET_REQUIRE(logits && target && sums && loss && ws && n > 0 && n <= 64 && k >= 1 && k <= 3 && h > 0 && w > 0 &&
+                    (long long)h * w < (1ll << 31) - LPIX,
+                "bce_dice_fwd: bad args (N <= 64, K <= 3)");
+  eunet_bce_dice_params prm;
+  if (!resolve(params, k, &prm, "bce_dice_fwd")) return EUNET_ERR_INVALID;
+  const int HW = h * w, tiles = cdiv(HW, LPIX);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(tiles, n);
+  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)target % 16 == 0);
+#define BF(KK)                                                                                                  \
+  if (vec)                                                                                                      \
+    bce_dice_fwd_kernel<KK, true><<<grid, NT, 0, s>>>(logits, target, HW, prm, (float*)ws);                     \
+  else                                                                                                          \
+    bce_dice_fwd_kernel<KK, false><<<grid, NT, 0, s>>>(logits, target, HW, prm, (float*)ws);                    \
+  bce_dice_finalize_kernel<KK><<<1, 256, 0, s>>>((const float*)ws, tiles, n, prm, sums, loss, parts);
+  if (k == 1) { BF(1) } else if (k == 2) { BF(2) } else { BF(3) }
+#undef BF
+  EUNET_LAUNCH_CHECK("bce_dice_fwd");
+  return EUNET_OK;
+}
+
+int eunet_bce_dice_bwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
+                       const eunet_bce_dice_params* params, const float* sums, const float* gloss, float* glogits,
+                       void* stream) {
+  EUNET_REQUIRE(logits && target && sums && gloss && glogits && n > 0 && n <= 64 && k >= 1 && k <= 3 && h > 0 &&
+                    w > 0 && (long long)h * w < (1ll << 31) - LPIX,
+                "bce_dice_bwd: bad args (N <= 64, K <= 3)");
+  eunet_bce_dice_params prm;
+  if (!resolve(params, k, &prm, "bce_dice_bwd")) return EUNET_ERR_INVALID;
+  const int HW = h * w;
+  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)target % 16 == 0) &&
+                   ((uintptr_t)glogits % 16 == 0);
+  const long long threads = (long long)n * HW / (vec ? 4 : 1);
+  const unsigned g = (unsigned)((threads + NT - 1) / NT);
+  hipStream_t s = (hipStream_t)stream;
+#define BB(KK)                                                                                        \
+  if (vec)                                                                                            \
+    bce_dice_bwd_kernel<KK, true><<<g, NT, 0, s>>>(logits, target, n, HW, prm, sums, gloss, glogits); \
+  else                                                                                                \
+    bce_dice_bwd_kernel<KK, false><<<g, NT, 0, s>>>(logits, target, n, HW, prm, sums, gloss, glogits);
+  if (k == 1) { BB(1) } else if (k == 2) { BB(2) } else { BB(3) }
+#undef BB
+  EUNET_LAUNCH_CHECK("bce_dice_bwd");
+  return EUNET_OK;
+}
+
+int eunet_sigmoid_crop(const float* logits, int k, int hp, int wp, int h, int w, int flip_h, int flip_w,
+                       float* probs, void* stream) {
+  EUNET_REQUIRE(logits && probs && k >= 1 && k <= 3 && h > 0 && w > 0 && h <= hp && w <= wp,
+                "sigmoid_crop: bad args (K must be 1..3, crop inside the map)");
+  const unsigned g = grid_for((long long)h * w);
+  hipStream_t s = (hipStream_t)stream;
+  if (k == 1) sigmoid_crop_kernel<1><<<g, NT, 0, s>>>(logits, hp, wp, h, w, flip_h, flip_w, probs);
+  else if (k == 2) sigmoid_crop_kernel<2><<<g, NT, 0, s>>>(logits, hp, wp, h, w, flip_h, flip_w, probs);
+  else sigmoid_crop_kernel<3><<<g, NT, 0, s>>>(logits, hp, wp, h, w, flip_h, flip_w, probs);
+  EUNET_LAUNCH_CHECK("sigmoid_crop");
+  return EUNET_OK;
+}
+
+int eunet_probs_threshold(const float* probs, int k, int h, int w, float threshold, int64_t* mask, void* stream) {
+  EUNET_REQUIRE(probs && mask && k >= 1 && k <= 3 && h > 0 && w > 0, "probs_threshold: bad args (K must be 1..3)");
+  const long long hw = (long long)h * w;
+  const unsigned g = grid_for(hw);
+  hipStream_t s = (hipStream_t)stream;
+  if (k == 1) probs_threshold_kernel<1><<<g, NT, 0, s>>>(probs, hw, threshold, mask);
+  else if (k == 2) probs_threshold_kernel<2><<<g, NT, 0, s>>>(probs, hw, threshold, mask);
+  else probs_threshold_kernel<3><<<g, NT, 0, s>>>(probs, hw, threshold, mask);
+  EUNET_LAUNCH_CHECK("probs_threshold");
+  return EUNET_OK;
+}
+
+}  // extern "C"

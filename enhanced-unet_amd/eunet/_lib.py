@@ -38,6 +38,16 @@ class LossParams(ctypes.Structure):
                 ("focal_norm", c_int)]
 
 
+class BCEDiceParams(ctypes.Structure):
+    """eunet_bce_dice_params (include/eunet.h): the configuration of one sigmoid BCE + Dice loss call."""
+    _fields_ = [("pos_weight", c_float * 3), ("class_weight", c_float * 3), ("dice_weight", c_float * 3),
+                ("w_bce", c_float), ("w_dice", c_float), ("smooth", c_float), ("ignore_index", c_int),
+                ("target_mode", c_int)]
+
+
+BCE_TARGET_AUTO, BCE_TARGET_ONEHOT, BCE_TARGET_FOREGROUND = 0, 1, 2  # EUNET_BCE_TARGET_*
+
+
 class OptTensor(ctypes.Structure):
     """eunet_opt_tensor (include/eunet.h): one parameter's data / grad / AdamW state / step counter."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
@@ -92,6 +102,11 @@ SIGNATURES = {
     "eunet_loss_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],
     "eunet_loss_fwd": [_f, _f, c_int, c_int, c_int, c_int, POINTER(LossParams), _f, _f, _f, _f, c_void_p],
     "eunet_loss_bwd": [_f, _f, c_int, c_int, c_int, c_int, POINTER(LossParams), _f, _f, _f, c_void_p],
+    "eunet_bce_dice_default_params": [POINTER(BCEDiceParams)],
+    "eunet_bce_dice_sums_len": [c_int, c_int, POINTER(c_int)],
+    "eunet_bce_dice_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],
+    "eunet_bce_dice_fwd": [_f, _f, c_int, c_int, c_int, c_int, POINTER(BCEDiceParams), _f, _f, _f, _f, c_void_p],
+    "eunet_bce_dice_bwd": [_f, _f, c_int, c_int, c_int, c_int, POINTER(BCEDiceParams), _f, _f, _f, c_void_p],
     "eunet_bn_bwd_tiles": [_P, POINTER(c_int)],
     "eunet_bn_bwd_reduce": [_P, _P, _f, _f, _f, _f, _f, c_void_p],
     "eunet_colsum_ws_bytes": [c_int, c_int, POINTER(c_size_t)],
@@ -116,6 +131,8 @@ SIGNATURES = {
     "eunet_softmax_crop": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_accumulate": [_f, _f, c_int64, c_int, c_float, c_void_p],
     "eunet_probs_to_mask": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
+    "eunet_sigmoid_crop": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
+    "eunet_probs_threshold": [_f, c_int, c_int, c_int, c_float, _f, c_void_p],
     "eunet_pack_masks": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
     "eunet_pack_masks_bbox": [_f, c_int, c_int, c_int, _f, _f, _f, c_void_p],
     "eunet_coco_match": [_f, _f, _f, _f, _f, _f, _f, c_int, c_int, POINTER(ctypes.c_double), c_int, _f, c_void_p],
@@ -257,5 +274,5 @@ def debug_status(reset: bool = False):
     return int(line.value), int(cnt.value)
 
 
-__all__ = ["Act", "LossParams", "load", "call", "EunetError", "EUNET_F32", "EUNET_BF16", "exported_symbols",
+__all__ = ["Act", "LossParams", "BCEDiceParams", "load", "call", "EunetError", "EUNET_F32", "EUNET_BF16", "exported_symbols",
            "c_int", "c_size_t", "c_float", "c_int64"]

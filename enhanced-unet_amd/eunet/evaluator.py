@@ -52,8 +52,8 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .metrics import (calculate_instance_metrics, calculate_semantic_metrics, calculate_viability_metrics,
-                      coco_image_matches, coco_map_from_matches)
+from .metrics import (calculate_dice, calculate_instance_metrics, calculate_iou, calculate_semantic_metrics,
+                      calculate_viability_metrics, coco_image_matches, coco_map_from_matches)
 
 TTA_SCALES = (0.75, 1.25)
 
@@ -91,7 +91,16 @@ def reference_preprocess(image: torch.Tensor) -> torch.Tensor:
 
 
 class Evaluator:
-    def __init__(self, model, device, model_name, preprocess: Union[str, Callable, None] = "reference"):
+    def __init__(self, model, device, model_name, preprocess: Union[str, Callable, None] = "reference", *,
+                 activation: str = "softmax", threshold: float = 0.5):
+        """activation "softmax" is the reference's path.  "sigmoid" is the prediction path of a model trained
+        with losses.bce_dice_loss: a sigmoid per logit (ops.sigmoid_crop), the same TTA mean of probabilities,
+        then ops.probs_threshold ([p >= threshold] for one logit, the argmax for more); the reference's
+        hand-tuned probs_to_mask rules are softmax-specific and are not applied."""
+        if activation not in ("softmax", "sigmoid"):
+            raise ValueError(f"activation must be 'softmax' or 'sigmoid', not {activation!r}")
+        self.activation = activation
+        self.threshold = float(threshold)
         self.model = model
         self.device = device
         self.model_name = model_name
@@ -126,6 +135,8 @@ class Evaluator:
         if h_pad or w_pad:
             x = F.pad(x, (0, w_pad, 0, h_pad), mode="reflect")
         logits = self._logits(x)[0]
+        if self.activation == "sigmoid":
+            return ops.sigmoid_crop(logits, h, w, flip_h=flip_h, flip_w=flip_w)
         return ops.softmax_crop(logits, h, w, flip_h=flip_h, flip_w=flip_w)
 
     # ---- train_eval.py:419-453 -------------------------------------------------
@@ -155,7 +166,10 @@ class Evaluator:
     def _convert_probs_to_mask(self, probs: torch.Tensor, h_pad: int = 0, w_pad: int = 0,
                                h_orig: int = None, w_orig: int = None) -> np.ndarray:
         probs = probs.to(self.device)
-        mask = ops.probs_to_mask(probs)
+        if self.activation == "sigmoid":
+            mask = ops.probs_threshold(probs, self.threshold)
+        else:
+            mask = ops.probs_to_mask(probs)
         if h_pad > 0 or w_pad > 0:
             mask = mask[:h_orig, :w_orig]
         return mask.cpu().numpy()
@@ -177,6 +191,24 @@ class Evaluator:
                 for k, v in calculate_semantic_metrics(pred, item["semantic_mask"]).items():
                     acc.setdefault(k, []).append(v)
         return {k: float(np.mean(v)) for k, v in acc.items()}
+
+    def evaluate_binary(self, dataloader) -> Dict[str, float]:
+        """For a one-logit sigmoid model: the means over the images of metrics.calculate_iou /
+        calculate_dice(pred == 1, semantic_mask > 0) as {"bin_iou", "bin_dice"}."""
+        if self.activation != "sigmoid":
+            raise ValueError("evaluate_binary is the evaluation of a sigmoid model: Evaluator(activation='sigmoid')")
+        k = getattr(self.model, "num_classes", None)
+        if k != 1:
+            raise ValueError(f"evaluate_binary needs a model of one logit (num_classes = 1), this one has {k}")
+        ious, dices = [], []
+        for batch in dataloader:
+            for i, item in enumerate(batch["batch_items"]):
+                pred = self.predict_semantic_mask(batch["images"][i])
+                gt = item["semantic_mask"]
+                gt = gt.cpu().numpy() if isinstance(gt, torch.Tensor) else np.asarray(gt)
+                ious.append(calculate_iou(pred == 1, gt > 0))
+                dices.append(calculate_dice(pred == 1, gt > 0))
+        return {"bin_iou": float(np.mean(ious)) if ious else 0.0, "bin_dice": float(np.mean(dices)) if dices else 0.0}
 
     # ---- train_eval.py:654-850 -------------------------------------------------
     def _split_large_region(self, region, area: int, final, next_label: int, min_area: int) -> int:

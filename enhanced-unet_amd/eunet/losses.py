@@ -14,6 +14,11 @@ synchronisation.  Here the kernel counts them on the device and check_targets() 
 ValueError at the next host synchronisation of the training loop (Trainer.step's
 loss.item(), the end of Trainer.train_epoch), or immediately with combined_loss(...,
 validate=True).
+
+bce_dice_loss / BCEDiceLoss are the sigmoid counterpart (csrc/bce_dice.hip): one logit per class, BCE
++ soft Dice, with K = 1 for foreground against background.  The reference has none (BASELINE.json's
+north star names it); include/eunet.h holds its definition.  It reports refused targets through the
+same counter and check_targets().
 """
 from __future__ import annotations
 
@@ -23,7 +28,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import LossParams
+from . import _lib
+from ._lib import BCEDiceParams, LossParams
 
 NO_IGNORE = -(2 ** 31)  # EUNET_NO_IGNORE
 
@@ -201,6 +207,121 @@ def combined_loss(logits: torch.Tensor, target: torch.Tensor, return_parts: bool
     return (loss, parts) if return_parts else loss
 
 
+# ---- sigmoid BCE + soft Dice (csrc/bce_dice.hip; no reference counterpart: BASELINE.json north star) ----
+TARGET_MODES = {None: _lib.BCE_TARGET_AUTO, "onehot": _lib.BCE_TARGET_ONEHOT,
+                "foreground": _lib.BCE_TARGET_FOREGROUND}
+
+
+def make_bce_dice_params(*, pos_weight=None, class_weight=None, dice_weight=None, w_bce: float = 1.0,
+                         w_dice: float = 1.0, smooth: float = 1e-6, ignore_index: Optional[int] = None,
+                         target_mode: Optional[str] = None) -> BCEDiceParams:
+    """eunet_bce_dice_params (include/eunet.h holds the definition of the loss).  The three tables as
+    _triple reads them: None means 1 for every class, a scalar applies to every class, a list or tensor
+    gives per-class values (at most 3).  target_mode: "onehot" (t_c = [target == c], K >= 2),
+    "foreground" (t_0 = [target >= 1], K = 1) or None: by the K of the logits at call time."""
+    if target_mode not in TARGET_MODES:
+        raise ValueError(f"target_mode must be 'onehot', 'foreground' or None, not {target_mode!r}")
+    if not float(smooth) > 0.0:
+        raise ValueError(f"smooth must be > 0, got {smooth}")
+    p = BCEDiceParams()
+    p.pos_weight[:] = _triple(pos_weight, 1.0, "pos_weight")
+    p.class_weight[:] = _triple(class_weight, 1.0, "class_weight")
+    p.dice_weight[:] = _triple(dice_weight, 1.0, "dice_weight")
+    p.w_bce, p.w_dice, p.smooth = float(w_bce), float(w_dice), float(smooth)
+    p.ignore_index = NO_IGNORE if ignore_index is None else int(ignore_index)
+    p.target_mode = TARGET_MODES[target_mode]
+    return p
+
+
+def check_bce_dice_mode(params: Optional[BCEDiceParams], k: int):
+    """The library's rule, raised on the host as ValueError: "foreground" is the mode of K = 1 and its
+    only one."""
+    mode = _lib.BCE_TARGET_AUTO if params is None else params.target_mode
+    if mode == _lib.BCE_TARGET_FOREGROUND and k != 1:
+        raise ValueError(f"target_mode 'foreground' needs K = 1, the logits have K = {k}")
+    if mode == _lib.BCE_TARGET_ONEHOT and k == 1:
+        raise ValueError("K = 1 has the target mode 'foreground' only")
+
+
+class BCEDiceFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, params, track_targets):
+        logits = logits.contiguous().float()
+        target = target.contiguous().long()
+        if logits.dim() != 4:
+            raise ValueError(f"expected [N, K, H, W] logits, got {tuple(logits.shape)}")
+        n, k, h, w = logits.shape
+        if target.shape != (n, h, w):
+            raise ValueError(f"target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+        check_bce_dice_mode(params, k)
+        if not logits.is_cuda or not target.is_cuda:
+            raise _lib.EunetError("bce_dice_loss needs device tensors (no CPU fallback)")
+        dev = logits.device
+        sums = torch.empty(ops.bce_dice_sums_len(n, k), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        ws = torch.empty(ops.bce_dice_workspace_bytes(n, k, h, w), dtype=torch.uint8, device=dev)
+        ops.bce_dice_fwd(logits, target, params, sums, loss, parts, ws)
+        if track_targets:
+            _record_bad(sums)
+        ctx.save_for_backward(logits, target, sums)
+        ctx.params = params
+        ctx.mark_non_differentiable(parts)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, gloss, gparts):
+        logits, target, sums = ctx.saved_tensors
+        glog = torch.empty_like(logits)
+        ops.bce_dice_bwd(logits, target, ctx.params, sums, gloss.contiguous().float().reshape(1), glog)
+        return glog, None, None, None
+
+
+def bce_dice_loss(logits: torch.Tensor, target: torch.Tensor, return_parts: bool = False,
+                  params: Optional[BCEDiceParams] = None, validate: bool = False, track_targets: bool = True):
+    """Sigmoid BCE + soft Dice: logits [N,K,H,W] (K = 1..3, N <= 64), target [N,H,W] ->
+    w_bce BCE + w_dice (1/N) sum_n dice_n (params: None = make_bce_dice_params()); parts [N,2] =
+    (bce_n, dice_n).  Pixels at ignore_index count nowhere; other invalid targets count nowhere either
+    and are reported by check_targets() (at once with validate=True)."""
+    loss, parts = BCEDiceFunction.apply(logits, target, params, track_targets)
+    if validate:
+        check_targets()
+    return (loss, parts) if return_parts else loss
+
+
+class BCEDiceLoss(nn.Module):
+    """bce_dice_loss with its configuration held as attributes (make_bce_dice_params' keywords): set them
+    at any time, the next call reads them."""
+
+    def __init__(self, pos_weight=None, class_weight=None, dice_weight=None, w_bce: float = 1.0,
+                 w_dice: float = 1.0, smooth: float = 1e-6, ignore_index: Optional[int] = None,
+                 target_mode: Optional[str] = None):
+        super().__init__()
+        self.pos_weight = pos_weight
+        self.class_weight = class_weight
+        self.dice_weight = dice_weight
+        self.w_bce = w_bce
+        self.w_dice = w_dice
+        self.smooth = smooth
+        self.ignore_index = ignore_index
+        self.target_mode = target_mode
+
+    def params(self, num_classes: Optional[int] = None) -> BCEDiceParams:
+        """The attributes as eunet_bce_dice_params; with num_classes the target mode is checked against it
+        and the default mode is resolved for it."""
+        p = make_bce_dice_params(pos_weight=self.pos_weight, class_weight=self.class_weight,
+                                 dice_weight=self.dice_weight, w_bce=self.w_bce, w_dice=self.w_dice,
+                                 smooth=self.smooth, ignore_index=self.ignore_index, target_mode=self.target_mode)
+        if num_classes is not None:
+            check_bce_dice_mode(p, num_classes)
+            if p.target_mode == _lib.BCE_TARGET_AUTO:
+                p.target_mode = _lib.BCE_TARGET_FOREGROUND if num_classes == 1 else _lib.BCE_TARGET_ONEHOT
+        return p
+
+    def forward(self, logits, target):
+        return bce_dice_loss(logits, target, params=self.params(logits.shape[1]))
+
+
 def _as_pixels(inputs: torch.Tensor, targets: torch.Tensor):
     """[N,K,*] logits / [N,*] targets -> [1,K,1,P] / [1,1,P] (pixel-mean losses only)."""
     if inputs.dim() < 2:
@@ -272,4 +393,5 @@ def tversky_loss(pred, target, num_classes: int = 3, alpha: float = 0.7):
 
 
 __all__ = ["combined_loss", "consistency_loss", "check_targets", "make_params", "reference_params", "FocalLoss",
-           "CrossEntropyLoss", "dice_loss", "tversky_loss"]
+           "CrossEntropyLoss", "dice_loss", "tversky_loss", "make_bce_dice_params", "BCEDiceFunction", "bce_dice_loss",
+           "BCEDiceLoss"]

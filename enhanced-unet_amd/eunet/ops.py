@@ -407,6 +407,81 @@ def loss_bwd(logits, target, params, sums, gloss, glogits):
          _ptr(glogits), _stream())
 
 
+# ---- sigmoid BCE + Dice loss (bce_dice.hip) ------------------------------------------------
+def bce_dice_default_params() -> _lib.BCEDiceParams:
+    p = _lib.BCEDiceParams()
+    call("eunet_bce_dice_default_params", ctypes.byref(p))
+    return p
+
+
+def bce_dice_sums_len(n, k):
+    v = c_int()
+    call("eunet_bce_dice_sums_len", n, k, ctypes.byref(v))
+    return v.value
+
+
+def bce_dice_workspace_bytes(n, k, h, w):
+    b = c_size_t()
+    call("eunet_bce_dice_workspace_bytes", n, k, h, w, ctypes.byref(b))
+    return b.value
+
+
+_bce_defaults = None  # the library's default parameters as _bce_flat gives them, read once
+
+
+def _bce_flat(p):
+    """eunet_bce_dice_params as the 14 scalars of the dispatcher schema (None: the library's defaults)."""
+    global _bce_defaults
+    if p is None:
+        if _bce_defaults is None:
+            _bce_defaults = _bce_flat(bce_dice_default_params())
+        return _bce_defaults
+    return (*p.pos_weight, *p.class_weight, *p.dice_weight, p.w_bce, p.w_dice, p.smooth, p.ignore_index,
+            p.target_mode)
+
+
+def _bce_struct(v):
+    p = _lib.BCEDiceParams()
+    p.pos_weight[:], p.class_weight[:], p.dice_weight[:] = v[0:3], v[3:6], v[6:9]
+    p.w_bce, p.w_dice, p.smooth, p.ignore_index, p.target_mode = v[9], v[10], v[11], v[12], v[13]
+    return p
+
+
+@_dispatched("T T f f f f f f f f f f f f i i T! T! T! T!")
+def bce_dice_fwd(logits, target, pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth,
+                 ignore_index, target_mode, sums, loss, parts, ws):
+    n, k, h, w = logits.shape
+    prm = _bce_struct((pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth, ignore_index,
+                       target_mode))
+    call("eunet_bce_dice_fwd", _ptr(logits), _ptr(target), n, k, h, w, ctypes.byref(prm), _ptr(sums), _ptr(loss),
+         _ptr(parts), _ptr(ws), _stream())
+
+
+@_dispatched("T T f f f f f f f f f f f f i i T T T!")
+def bce_dice_bwd(logits, target, pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth,
+                 ignore_index, target_mode, sums, gloss, glogits):
+    n, k, h, w = logits.shape
+    prm = _bce_struct((pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth, ignore_index,
+                       target_mode))
+    call("eunet_bce_dice_bwd", _ptr(logits), _ptr(target), n, k, h, w, ctypes.byref(prm), _ptr(sums), _ptr(gloss),
+         _ptr(glogits), _stream())
+
+
+# the dispatcher ops take the struct spread over scalars (a float of the struct survives the round trip
+# through the schema's double); the module's functions of the same names take the struct
+_bce_dice_fwd_op, _bce_dice_bwd_op = bce_dice_fwd, bce_dice_bwd
+
+
+def bce_dice_fwd(logits, target, params, sums, loss, parts, ws):
+    """torch.ops.eunet.bce_dice_fwd; params: _lib.BCEDiceParams or None (the library's defaults)."""
+    _bce_dice_fwd_op(logits, target, *_bce_flat(params), sums, loss, parts, ws)
+
+
+def bce_dice_bwd(logits, target, params, sums, gloss, glogits):
+    """torch.ops.eunet.bce_dice_bwd: glogits = gloss * d loss / d logits from the forward's sums."""
+    _bce_dice_bwd_op(logits, target, *_bce_flat(params), sums, gloss, glogits)
+
+
 def bn_bwd_tiles(y: Act) -> int:
     t = c_int()
     call("eunet_bn_bwd_tiles", ctypes.byref(y), ctypes.byref(t))
@@ -649,6 +724,40 @@ def probs_to_mask(probs):
     mask = torch.empty(h, w, dtype=torch.int64, device=probs.device)
     ws = torch.empty(2, dtype=torch.int64, device=probs.device)
     call("eunet_probs_to_mask", _ptr(probs), k, h, w, _ptr(mask), _ptr(ws), _stream())
+    return mask
+
+
+@_dispatched("T i i b b T!")
+def sigmoid_crop(logits, h, w, flip_h, flip_w, out):
+    k, hp, wp = logits.shape
+    call("eunet_sigmoid_crop", _ptr(logits), k, hp, wp, h, w, int(flip_h), int(flip_w), _ptr(out), _stream())
+
+
+_sigmoid_crop_op = sigmoid_crop  # torch.ops.eunet.sigmoid_crop writes into out; the function below allocates it
+
+
+def sigmoid_crop(logits, h, w, flip_h=False, flip_w=False, out=None):
+    """logits [K, hp, wp] fp32 (K = 1..3) -> sigmoid probs [K, h, w]: softmax_crop's crop and flips."""
+    logits = logits.contiguous().float()
+    y = out if out is not None else torch.empty(logits.shape[0], h, w, dtype=torch.float32, device=logits.device)
+    _sigmoid_crop_op(logits, h, w, bool(flip_h), bool(flip_w), y)
+    return y
+
+
+@_dispatched("T f T!")
+def probs_threshold(probs, threshold, mask):
+    k, h, w = probs.shape
+    call("eunet_probs_threshold", _ptr(probs), k, h, w, float(threshold), _ptr(mask), _stream())
+
+
+_probs_threshold_op = probs_threshold
+
+
+def probs_threshold(probs, threshold: float = 0.5):
+    """probs [K, h, w] fp32 -> int64 mask [h, w]: K = 1 [p >= threshold]; K >= 2 the argmax (first maximum)."""
+    probs = probs.contiguous().float()
+    mask = torch.empty(probs.shape[1:], dtype=torch.int64, device=probs.device)
+    _probs_threshold_op(probs, float(threshold), mask)
     return mask
 
 

@@ -263,6 +263,61 @@ int eunet_loss_bwd(const float* logits, const int64_t* target, int n, int k, int
                    const eunet_loss_params* params, const float* sums, const float* gloss, float* glogits,
                    void* stream);
 
+/* ---- sigmoid BCE + soft Dice loss (bce_dice.hip) ---------------------------
+ * No reference line to cite: the reference has no BCE.  The source is the
+ * project's own statement of purpose, BASELINE.json north_star ("BCE/Dice"); this comment is the
+ * definition.  logits x [N,K,H,W] fp32 NCHW, target [N,H,W] int64; K = 1..3, N <= 64 (as
+ * eunet_loss_fwd; anything else: EUNET_ERR_INVALID).  One logit per class, a sigmoid each.
+ *   target_mode ONEHOT (K >= 2):      t_c = [target == c],  valid iff 0 <= target < K
+ *   target_mode FOREGROUND (K = 1):   t_0 = [target >= 1],  valid iff target >= 0  (a 0/1/2
+ *                                     background/live/dead mask trains "cell")
+ *   target_mode AUTO: FOREGROUND for K = 1, ONEHOT otherwise.  FOREGROUND with K != 1, ONEHOT
+ *   with K = 1 and smooth <= 0 are EUNET_ERR_INVALID.
+ * A pixel equal to ignore_index contributes to nothing: not to the BCE sum, not to its
+ * denominator, not to I, S or T (eunet_loss_fwd differs: there an ignored pixel's probability still
+ * counts in S).  A pixel that is neither valid nor ignored contributes nothing either and is
+ * counted; the count is the last element of sums, where eunet_loss_fwd puts it.
+ *   sp(z) = max(z, 0) + log1p(exp(-|z|)), sig = sigmoid, V_n = valid pixels of sample n, V = sum V_n
+ *   bce(x,t)_c = cw_c (pw_c t sp(-x) + (1 - t) sp(x))
+ *                (F.binary_cross_entropy_with_logits(weight = cw, pos_weight = pw))
+ *   BCE    = sum_{n, c, valid px} bce / (K max(1, V))
+ *   bce_n  = sum_{c, valid px of n} bce / (K max(1, V_n))
+ *   per (n, c) over valid pixels: I = sum sig(x) t, S = sum sig(x), T = sum t
+ *   dice_n = (1/K) sum_c dw_c (1 - (2 I + smooth) / (S + T + smooth))
+ *   loss   = w_bce BCE + w_dice (1/N) sum_n dice_n
+ * A batch without a valid pixel gives loss 0 and gradient 0.
+ * sums (caller-owned, saved for backward): eunet_bce_dice_sums_len floats = [N][3+3K] rows of
+ * (bce sum, I[K], S[K], T[K], V_n, out-of-range count), then V, then the out-of-range count of
+ * the batch.  loss: 1 fp32 on device.  parts (nullable): [N][2] = (bce_n, dice_n).
+ * ws: eunet_bce_dice_workspace_bytes.  The sums are taken in a fixed order: two runs are
+ * bit-identical. */
+enum { EUNET_BCE_TARGET_AUTO = 0, EUNET_BCE_TARGET_ONEHOT = 1, EUNET_BCE_TARGET_FOREGROUND = 2 };
+typedef struct {
+  float pos_weight[3];   /* pw: weight of the positive term per class; 1 = none */
+  float class_weight[3]; /* cw: weight of a class's BCE; 1 = none */
+  float dice_weight[3];  /* dw: weight of a class's Dice term; 1 = none */
+  float w_bce, w_dice;   /* term weights */
+  float smooth;          /* Dice smoothing, > 0 (1e-6: Trainer.dice_loss's, train_eval.py:134-157) */
+  int ignore_index;      /* EUNET_NO_IGNORE = none */
+  int target_mode;       /* EUNET_BCE_TARGET_* */
+} eunet_bce_dice_params;
+/* pw = cw = dw = 1, w_bce = w_dice = 1, smooth 1e-6, no ignore index, target_mode AUTO (what a
+ * null params pointer means) */
+int eunet_bce_dice_default_params(eunet_bce_dice_params* params);
+int eunet_bce_dice_sums_len(int n, int k, int* len);
+int eunet_bce_dice_workspace_bytes(int n, int k, int h, int w, size_t* bytes);
+int eunet_bce_dice_fwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
+                       const eunet_bce_dice_params* params, float* sums, float* loss, float* parts, void* ws,
+                       void* stream);
+/* glogits = (*gloss) d loss / d logits (gloss: device scalar g), analytic per pixel from sums, with
+ * U = S + T + smooth:
+ *   g [ w_bce cw_c (-pw_c t sig(-x) + (1 - t) sig(x)) / (K max(1, V))
+ *       + w_dice dw_c / (N K) (-2 t / U + (2 I + smooth) / U^2) sig(x) sig(-x) ]
+ * and 0 on ignored and out-of-range pixels. */
+int eunet_bce_dice_bwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
+                       const eunet_bce_dice_params* params, const float* sums, const float* gloss, float* glogits,
+                       void* stream);
+
 /* ---- backward helpers ----------------------------------------------------
  * BN(+ReLU) backward (autograd of models.py:220-224): g is the gradient w.r.t.
  * the ReLU output, y the pre-BN conv output, mean / invstd the batch statistics and
@@ -395,6 +450,15 @@ int eunet_accumulate(float* acc, const float* p, long long n, int mode, float co
  * zero dead-cell probability) -> mask int64 [h][w]; counts: 2 int64 of workspace. */
 int eunet_probs_to_mask(const float* probs, int k, int h, int w, int64_t* mask,
                         int64_t* counts, void* stream);
+/* The prediction path of a model trained with eunet_bce_dice_fwd (no reference line: BASELINE.json
+ * north_star "BCE/Dice").  eunet_sigmoid_crop is eunet_softmax_crop's sibling: sigmoid of each of the
+ * K (1..3) logits [K][hp][wp], cropped to [h][w] and optionally flipped -> probs [K][h][w].
+ * eunet_probs_threshold: probs [K][h][w] -> mask int64 [h][w]; K = 1: [p >= threshold]; K >= 2:
+ * the argmax over K, the first maximum on ties (threshold unused). */
+int eunet_sigmoid_crop(const float* logits, int k, int hp, int wp, int h, int w, int flip_h,
+                       int flip_w, float* probs, void* stream);
+int eunet_probs_threshold(const float* probs, int k, int h, int w, float threshold, int64_t* mask,
+                          void* stream);
 
 /* ---- instance-level evaluation (instances.hip) ------------------------------
  * Pairwise mask overlap (metrics.py:61-194, calculate_instance_metrics: the calculate_iou
