@@ -18,16 +18,6 @@ constexpr int SFH = 16;           // forward tile SFH x STW = conv3x3 forward ti
 constexpr int SCI = 8;            // max input channels of the direct conv (enc1.0: in_ch; fusion_head.0: 2K)
 constexpr int SJT = (SCI * 9 + 15) / 16;  // 16-column im2col MFMA tiles of its wgrad (5)
 
-bool act_ok(const eunet_act* a) {
-  return a && a->ptr && a->n > 0 && a->h > 0 && a->w > 0 && a->c > 0 && a->coff >= 0 &&
-         a->coff + a->c <= a->ctot && (a->dtype == EUNET_F32 || a->dtype == EUNET_BF16);
-}
-int e16(int dt) { return dt == EUNET_BF16 ? 8 : 4; }
-bool vec_ok(const eunet_act* a) {
-  const int E = e16(a->dtype);
-  return a->c % E == 0 && a->ctot % E == 0 && a->coff % E == 0;
-}
-
 // ---------------------------------------------------------------------------
 // enc1.0 / fusion_head.0: direct 3x3 conv for Cin <= 8, 64 output channels per block.y
 // ---------------------------------------------------------------------------
@@ -1322,12 +1312,7 @@ __global__ __launch_bounds__(256) void up_bwd_k2_kernel(const float2* g, float2*
 // sums stay in registers over the block's C1X_PIX pixels.
 constexpr int C1X_PIX = 1024;
 // J = 1 (C <= 64) or 2 (C <= 128): the per-lane state (BN constants, 1x1 weights, partial sums)
-// is sized by it, so the 64-channel dec2 output runs at twice the occupancy
-#define C1X_LAUNCH(kern, T, BNR, ARGS)                                                       \
-  do {                                                                                       \
-    if (y->c <= 64) kern<T, 1, BNR><<<tiles, NT, 0, (hipStream_t)stream>>> ARGS;             \
-    else kern<T, 2, BNR><<<tiles, NT, 0, (hipStream_t)stream>>> ARGS;                        \
-  } while (0)
+// is sized by it, so the 64-channel dec2 output runs at twice the occupancy (conv1x1_bwd_launch)
 // sum over the 8 pixel slots of a wave (lanes l, l^8, l^16, l^32, ...): DPP row rotate by 8 within
 // each 16-lane row, then the gfx950 permlane16 / permlane32 swaps (no ds_bpermute round trips)
 __device__ __forceinline__ float sum_slots8(float v) {
@@ -1521,6 +1506,76 @@ int eunet_colsum_ld(const float* part, int rows, int cols, int ld, float* out, v
   return eunet_colsum_segs(part, rows, cols, ld, g, ws, s);
 }
 
+// ---- launch helpers of the entry points below (templates: outside the extern "C" block) ----
+namespace {
+// block size of the fused BN-backward reductions: the block's threads must cover whole channel units
+// (a thread's unit is fixed across the grid-stride loop) -- 256 threads, or 192 for the channel counts
+// of base 96 (96 / 192 / 384 / 768 channels: 12 / 24 / 48 / 96 bf16 units); 0: not fusable
+int bnr_block(const eunet_act* g) {
+  const int U = g->c / elems16(g->dtype);
+  return U > 0 && NT % U == 0 ? NT : (U > 0 && 192 % U == 0 ? 192 : 0);
+}
+bool bnr_ok(const eunet_act* g, const eunet_act* y) {
+  return act_ok(y) && vec_ok(y) && like(y, g) && bnr_block(g) > 0;
+}
+long long pool_threads(const eunet_act* gout) {
+  return (long long)gout->n * (gout->h / 2) * (gout->w / 2) * (gout->c / elems16(gout->dtype));
+}
+// fused-reduction grid, which is also the number of partial rows: at most cap blocks (each thread
+// then covers several outputs).  Measured: the max-pool adjoint prefers 2048 (fewer rows to write
+// and sum), the upsample adjoint, with more work per output, 8192 (more loads in flight).
+int bnr_grid(long long threads, int cap, int block) { return (int)std::min<long long>((threads + block - 1) / block, cap); }
+long long up_threads(const eunet_act* glo) {
+  return (long long)glo->n * ((glo->h + UP_R - 1) / UP_R) * ((glo->w + 1) / 2) * (glo->c / elems16(glo->dtype));
+}
+
+// what both max-pool adjoints require of their inputs: gpool is act's half, the optional gskip is like act
+bool pool_bwd_inputs_ok(const eunet_act* act, const eunet_act* gpool, const eunet_act* gskip) {
+  return act_ok(gpool) && vec_ok(gpool) && same_dtype(gpool, act) && is_2x(act, gpool) && gpool->c == act->c &&
+         (!gskip || (act_ok(gskip) && vec_ok(gskip) && like(gskip, act)));
+}
+// the max-pool adjoint, plain or (BNR) with the fused BN-backward reduction br; gskip may be null, and with BNR
+// gout's ptr may be (reduce only)
+template <bool BNR>
+void pool_bwd_add_launch(const eunet_act* act, const eunet_act* gpool, const eunet_act* gskip, const eunet_act* gout,
+                         const BnRed& br, unsigned grid, int block, void* stream) {
+  by_dtype(act->dtype, [&](auto t) {
+    using T = decltype(t);
+    pool_bwd_add_kernel<T, BNR><<<grid, block, 0, (hipStream_t)stream>>>(
+        act_ptr<const T>(act), act->ctot, act->coff, act_ptr<const T>(gpool), gpool->ctot, gpool->coff,
+        act_ptr<const T>(gskip), gskip ? gskip->ctot : 0, gskip ? gskip->coff : 0, act_ptr<T>(gout), gout->ctot,
+        gout->coff, act->n, act->h, act->w, act->c, br);
+  });
+}
+// the vector upsample adjoint, plain or (BNR) with the fused BN-backward reduction br
+template <bool BNR>
+void up_bwd_rows_launch(const eunet_act* ghi, const eunet_act* glo, const BnRed& br, unsigned grid, int block,
+                        void* stream) {
+  by_dtype(ghi->dtype, [&](auto t) {
+    using T = decltype(t);
+    up_bwd_rows_kernel<T, T, BNR><<<grid, block, 0, (hipStream_t)stream>>>(
+        act_ptr<const T>(ghi), ghi->ctot, ghi->coff, act_ptr<T>(glo), glo->ctot, glo->coff, glo->n, glo->h, glo->w,
+        glo->c, br);
+  });
+}
+// dec1 backward, plain or (BNR) with the BN-backward reduction (bmean, bistd -> bpart); gact may be null with
+// BNR (reduce only).  J = 1 (C <= 64) or 2 channel halves per lane group (conv1x1_bwd_kernel)
+template <bool BNR>
+void conv1x1_bwd_launch(const eunet_act* y, const float* scale, const float* shift, const float* w, int k,
+                        const float* gz, const eunet_act* gact, float* part, const float* bmean, const float* bistd,
+                        float* bpart, void* stream) {
+  const long long P = (long long)y->n * y->h * y->w;
+  const unsigned tiles = (unsigned)((P + C1X_PIX - 1) / C1X_PIX);
+  by_dtype(y->dtype, [&](auto t) {
+    using T = decltype(t);
+    auto kern = y->c <= 64 ? conv1x1_bwd_kernel<T, 1, BNR> : conv1x1_bwd_kernel<T, 2, BNR>;
+    kern<<<tiles, NT, 0, (hipStream_t)stream>>>(act_ptr<const T>(y), P, y->c, y->ctot, y->coff, scale, shift, w, k, gz,
+                                                act_ptr<T>(gact), gact ? gact->ctot : 0, gact ? gact->coff : 0, part,
+                                                bmean, bistd, bpart);
+  });
+}
+}  // namespace
+
 extern "C" {
 
 int eunet_nchw_to_nhwc(const float* x, const eunet_act* out, void* stream);
@@ -1528,22 +1583,19 @@ int eunet_nchw_to_nhwc(const float* x, const eunet_act* out, void* stream);
 int eunet_conv_small_fwd(const eunet_act* x, const float* w, const float* bias, const eunet_act* y, float* stats,
                          void* stream) {
   EUNET_REQUIRE(act_ok(x) && act_ok(y) && w, "conv_small_fwd: bad args");
-  EUNET_REQUIRE(x->c <= SCI && x->dtype == y->dtype, "conv_small_fwd: Cin <= 8 and equal dtypes required");
-  EUNET_REQUIRE(x->n == y->n && x->h == y->h && x->w == y->w, "conv_small_fwd: spatial mismatch");
+  EUNET_REQUIRE(x->c <= SCI && same_dtype(x, y), "conv_small_fwd: Cin <= 8 and equal dtypes required");
+  EUNET_REQUIRE(same_nhw(x, y), "conv_small_fwd: spatial mismatch");
   SmallArgs a;
   a.x = x->ptr; a.N = x->n; a.H = x->h; a.W = x->w; a.xct = x->ctot; a.xco = x->coff; a.cin = x->c;
   a.w = w; a.b = bias;
   a.y = y->ptr; a.yct = y->ctot; a.yco = y->coff; a.cout = y->c;
   a.stats = stats; a.tx = cdiv(x->w, STW); a.ty = cdiv(x->h, SFH); a.ntiles = x->n * a.tx * a.ty;
   dim3 grid(a.ntiles, cdiv(y->c, 64));
-  const bool c1 = x->c == 1;
-  if (x->dtype == EUNET_BF16) {
-    if (c1) conv_small_fwd_kernel<bf16_t, true><<<grid, NT, 0, (hipStream_t)stream>>>(a);
-    else conv_small_fwd_kernel<bf16_t, false><<<grid, NT, 0, (hipStream_t)stream>>>(a);
-  } else {
-    if (c1) conv_small_fwd_kernel<float, true><<<grid, NT, 0, (hipStream_t)stream>>>(a);
-    else conv_small_fwd_kernel<float, false><<<grid, NT, 0, (hipStream_t)stream>>>(a);
-  }
+  by_dtype(x->dtype, [&](auto t) {
+    using T = decltype(t);
+    auto kern = x->c == 1 ? conv_small_fwd_kernel<T, true> : conv_small_fwd_kernel<T, false>;
+    kern<<<grid, NT, 0, (hipStream_t)stream>>>(a);
+  });
   EUNET_LAUNCH_CHECK("conv_small_fwd");
   return EUNET_OK;
 }
@@ -1562,10 +1614,10 @@ int eunet_conv_small_wgrad_splits(const eunet_act* dy, int* nsplit) {
 int eunet_conv_small_wgrad(const eunet_act* x, const eunet_act* dy, float* dw_part, float* db_part, int nsplit,
                            void* stream) {
   EUNET_REQUIRE(act_ok(x) && act_ok(dy) && dw_part && nsplit > 0, "conv_small_wgrad: bad args");
-  EUNET_REQUIRE(x->c <= SCI && x->dtype == dy->dtype, "conv_small_wgrad: Cin <= 8, equal dtypes");
+  EUNET_REQUIRE(x->c <= SCI && same_dtype(x, dy), "conv_small_wgrad: Cin <= 8, equal dtypes");
   // the dY tile is staged in whole 16-byte units
   EUNET_REQUIRE(vec_ok(dy), "conv_small_wgrad: dy channels, slot and row stride must be multiples of a 16-byte unit");
-  EUNET_REQUIRE(x->n == dy->n && x->h == dy->h && x->w == dy->w, "conv_small_wgrad: spatial mismatch");
+  EUNET_REQUIRE(same_nhw(x, dy), "conv_small_wgrad: spatial mismatch");
   SmallWgArgs a;
   a.x = x->ptr; a.N = x->n; a.H = x->h; a.W = x->w; a.xct = x->ctot; a.xco = x->coff; a.cin = x->c;
   a.dy = dy->ptr; a.dct = dy->ctot; a.dco = dy->coff; a.cout = dy->c;
@@ -1574,16 +1626,11 @@ int eunet_conv_small_wgrad(const eunet_act* x, const eunet_act* dy, float* dw_pa
   a.per_split = cdiv(a.ntiles, nsplit);
   EUNET_REQUIRE(cdiv(a.ntiles, a.per_split) == nsplit, "conv_small_wgrad: nsplit mismatch");
   dim3 grid(nsplit, cdiv(dy->c, 64));
-  if (x->dtype == EUNET_BF16)
-    if (x->c <= 4)
-      conv_small_wgrad_kernel<bf16_t, 4><<<grid, NT, 0, (hipStream_t)stream>>>(a);
-    else
-      conv_small_wgrad_kernel<bf16_t, 8><<<grid, NT, 0, (hipStream_t)stream>>>(a);
-  else
-    if (x->c <= 4)
-      conv_small_wgrad_kernel<float, 4><<<grid, NT, 0, (hipStream_t)stream>>>(a);
-    else
-      conv_small_wgrad_kernel<float, 8><<<grid, NT, 0, (hipStream_t)stream>>>(a);
+  by_dtype(x->dtype, [&](auto t) {
+    using T = decltype(t);
+    auto kern = x->c <= 4 ? conv_small_wgrad_kernel<T, 4> : conv_small_wgrad_kernel<T, 8>;
+    kern<<<grid, NT, 0, (hipStream_t)stream>>>(a);
+  });
   EUNET_LAUNCH_CHECK("conv_small_wgrad");
   return EUNET_OK;
 }
@@ -1610,16 +1657,14 @@ int eunet_bn_eval_affine(int c, const float* gamma, const float* beta, const flo
 
 int eunet_bnrelu(const eunet_act* y, const float* scale, const float* shift, const eunet_act* out, void* stream) {
   EUNET_REQUIRE(act_ok(y) && act_ok(out) && scale && shift && vec_ok(y) && vec_ok(out), "bnrelu: bad args");
-  EUNET_REQUIRE(out->n == y->n && out->h == y->h && out->w == y->w && out->c == y->c && out->dtype == y->dtype,
-                "bnrelu: shape mismatch");
-  const long long P = (long long)y->n * y->h * y->w, total = P * (y->c / e16(y->dtype));
+  EUNET_REQUIRE(like(out, y), "bnrelu: shape mismatch");
+  const long long P = (long long)y->n * y->h * y->w, total = P * (y->c / elems16(y->dtype));
   const unsigned g = (unsigned)std::min<long long>((total + 255) / 256, 16384);
-  if (y->dtype == EUNET_BF16)
-    bnrelu_kernel<bf16_t><<<g, 256, 0, (hipStream_t)stream>>>((const bf16_t*)y->ptr, P, y->c, y->ctot, y->coff,
-                                                            scale, shift, (bf16_t*)out->ptr, out->ctot, out->coff);
-  else
-    bnrelu_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>((const float*)y->ptr, P, y->c, y->ctot, y->coff,
-                                                           scale, shift, (float*)out->ptr, out->ctot, out->coff);
+  by_dtype(y->dtype, [&](auto t) {
+    using T = decltype(t);
+    bnrelu_kernel<T><<<g, 256, 0, (hipStream_t)stream>>>(act_ptr<const T>(y), P, y->c, y->ctot, y->coff, scale, shift,
+                                                       act_ptr<T>(out), out->ctot, out->coff);
+  });
   EUNET_LAUNCH_CHECK("bnrelu");
   return EUNET_OK;
 }
@@ -1629,23 +1674,16 @@ int eunet_bnrelu_pool(const eunet_act* y, const float* scale, const float* shift
   EUNET_REQUIRE(act_ok(y) && act_ok(pooled) && scale && shift && vec_ok(y) && vec_ok(pooled),
                 "bnrelu_pool: bad args");
   EUNET_REQUIRE(y->h % 2 == 0 && y->w % 2 == 0, "bnrelu_pool: H and W must be even");
-  EUNET_REQUIRE(pooled->h == y->h / 2 && pooled->w == y->w / 2 && pooled->c == y->c && pooled->n == y->n,
-                "bnrelu_pool: pooled shape");
-  if (act) EUNET_REQUIRE(act_ok(act) && vec_ok(act) && act->h == y->h && act->w == y->w && act->c == y->c,
-                         "bnrelu_pool: act shape");
-  const int E = e16(y->dtype);
-  const long long total = (long long)y->n * (y->h / 2) * (y->w / 2) * (y->c / E);
+  EUNET_REQUIRE(is_2x(y, pooled) && pooled->c == y->c && same_dtype(pooled, y), "bnrelu_pool: pooled shape");
+  if (act) EUNET_REQUIRE(act_ok(act) && vec_ok(act) && like(act, y), "bnrelu_pool: act shape");
+  const long long total = (long long)y->n * (y->h / 2) * (y->w / 2) * (y->c / elems16(y->dtype));
   const unsigned g = (unsigned)((total + 255) / 256);
-  if (y->dtype == EUNET_BF16)
-    bnrelu_pool_kernel<bf16_t><<<g, 256, 0, (hipStream_t)stream>>>(
-        (const bf16_t*)y->ptr, y->n, y->h, y->w, y->c, y->ctot, y->coff, scale, shift,
-        act ? (bf16_t*)act->ptr : nullptr, act ? act->ctot : 0, act ? act->coff : 0, (bf16_t*)pooled->ptr,
-        pooled->ctot, pooled->coff);
-  else
-    bnrelu_pool_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>(
-        (const float*)y->ptr, y->n, y->h, y->w, y->c, y->ctot, y->coff, scale, shift,
-        act ? (float*)act->ptr : nullptr, act ? act->ctot : 0, act ? act->coff : 0, (float*)pooled->ptr,
-        pooled->ctot, pooled->coff);
+  by_dtype(y->dtype, [&](auto t) {
+    using T = decltype(t);
+    bnrelu_pool_kernel<T><<<g, 256, 0, (hipStream_t)stream>>>(
+        act_ptr<const T>(y), y->n, y->h, y->w, y->c, y->ctot, y->coff, scale, shift, act_ptr<T>(act),
+        act ? act->ctot : 0, act ? act->coff : 0, act_ptr<T>(pooled), pooled->ctot, pooled->coff);
+  });
   EUNET_LAUNCH_CHECK("bnrelu_pool");
   return EUNET_OK;
 }
@@ -1653,23 +1691,19 @@ int eunet_bnrelu_pool(const eunet_act* y, const float* scale, const float* shift
 int eunet_bnrelu_upsample(const eunet_act* y, const float* scale, const float* shift, const eunet_act* out,
                           void* stream) {
   EUNET_REQUIRE(act_ok(y) && act_ok(out) && scale && shift && vec_ok(y) && vec_ok(out), "bnrelu_upsample: bad args");
-  EUNET_REQUIRE(out->h == 2 * y->h && out->w == 2 * y->w && out->c == y->c && out->n == y->n &&
-                    out->dtype == y->dtype,
-                "bnrelu_upsample: shape");
-  const int E = e16(y->dtype);
+  EUNET_REQUIRE(is_2x(out, y) && out->c == y->c && same_dtype(out, y), "bnrelu_upsample: shape");
+  const int E = elems16(y->dtype);
   // rows per thread: 8, or 4 when the grid would have fewer than 4096 blocks (measured: 2 rows per thread is slower)
   int rpt = 8;
   auto blocks = [&](int r) { return ((long long)y->n * cdiv(y->h, r) * ((y->w + 1) / 2) * (y->c / E) + 255) / 256; };
   if (blocks(rpt) < 4096) rpt = 4;
   const unsigned g = (unsigned)blocks(rpt);
-  if (y->dtype == EUNET_BF16)
-    bnrelu_up_rows_kernel<bf16_t><<<g, 256, 0, (hipStream_t)stream>>>(
-        (const bf16_t*)y->ptr, y->n, y->h, y->w, y->c, y->ctot, y->coff, scale, shift, (bf16_t*)out->ptr,
-        out->ctot, out->coff, rpt);
-  else
-    bnrelu_up_rows_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>(
-        (const float*)y->ptr, y->n, y->h, y->w, y->c, y->ctot, y->coff, scale, shift, (float*)out->ptr,
-        out->ctot, out->coff, rpt);
+  by_dtype(y->dtype, [&](auto t) {
+    using T = decltype(t);
+    bnrelu_up_rows_kernel<T><<<g, 256, 0, (hipStream_t)stream>>>(act_ptr<const T>(y), y->n, y->h, y->w, y->c, y->ctot,
+                                                               y->coff, scale, shift, act_ptr<T>(out), out->ctot,
+                                                               out->coff, rpt);
+  });
   EUNET_LAUNCH_CHECK("bnrelu_upsample");
   return EUNET_OK;
 }
@@ -1682,12 +1716,11 @@ int eunet_bnrelu_conv1x1(const eunet_act* y, const float* scale, const float* sh
   const long long P = (long long)y->n * y->h * y->w;
   const long long nb = (P + 32 * C1X_PX - 1) / (32 * C1X_PX);
   const unsigned g = (unsigned)(nb < 8192 ? nb : 8192);
-  if (y->dtype == EUNET_BF16)
-    bnrelu_conv1x1_kernel<bf16_t><<<g, 256, 0, (hipStream_t)stream>>>((const bf16_t*)y->ptr, P, y->c, y->ctot,
-                                                                        y->coff, scale, shift, w, b, k, z);
-  else
-    bnrelu_conv1x1_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>((const float*)y->ptr, P, y->c, y->ctot,
-                                                                       y->coff, scale, shift, w, b, k, z);
+  by_dtype(y->dtype, [&](auto t) {
+    using T = decltype(t);
+    bnrelu_conv1x1_kernel<T><<<g, 256, 0, (hipStream_t)stream>>>(act_ptr<const T>(y), P, y->c, y->ctot, y->coff, scale,
+                                                               shift, w, b, k, z);
+  });
   EUNET_LAUNCH_CHECK("bnrelu_conv1x1");
   return EUNET_OK;
 }
@@ -1703,20 +1736,17 @@ int eunet_bn_bwd_reduce(const eunet_act* g, const eunet_act* y, const float* mea
                         const float* scale, const float* shift, float* part, void* stream) {
   EUNET_REQUIRE(act_ok(g) && act_ok(y) && vec_ok(g) && vec_ok(y) && mean && invstd && scale && shift && part,
                 "bn_bwd_reduce: bad args");
-  EUNET_REQUIRE(g->dtype == y->dtype && g->c == y->c && g->n == y->n && g->h == y->h && g->w == y->w,
-                "bn_bwd_reduce: shape mismatch");
-  EUNET_REQUIRE(y->c / e16(y->dtype) <= NT, "bn_bwd_reduce: too many channels");
+  EUNET_REQUIRE(like(g, y), "bn_bwd_reduce: shape mismatch");
+  EUNET_REQUIRE(y->c / elems16(y->dtype) <= NT, "bn_bwd_reduce: too many channels");
   const long long P = (long long)y->n * y->h * y->w;
   const int tpix = (int)bwd_pix(P);
   const unsigned tiles = (unsigned)((P + tpix - 1) / tpix);
-  if (y->dtype == EUNET_BF16)
-    bn_bwd_reduce_kernel<bf16_t><<<tiles, NT, 0, (hipStream_t)stream>>>(
-        (const bf16_t*)g->ptr, g->ctot, g->coff, (const bf16_t*)y->ptr, y->ctot, y->coff, P, y->c, mean, invstd,
-        scale, shift, part, tpix);
-  else
-    bn_bwd_reduce_kernel<float><<<tiles, NT, 0, (hipStream_t)stream>>>(
-        (const float*)g->ptr, g->ctot, g->coff, (const float*)y->ptr, y->ctot, y->coff, P, y->c, mean, invstd,
-        scale, shift, part, tpix);
+  by_dtype(y->dtype, [&](auto t) {
+    using T = decltype(t);
+    bn_bwd_reduce_kernel<T><<<tiles, NT, 0, (hipStream_t)stream>>>(act_ptr<const T>(g), g->ctot, g->coff,
+                                                                 act_ptr<const T>(y), y->ctot, y->coff, P, y->c, mean,
+                                                                 invstd, scale, shift, part, tpix);
+  });
   EUNET_LAUNCH_CHECK("bn_bwd_reduce");
   return EUNET_OK;
 }
@@ -1743,22 +1773,19 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
   EUNET_REQUIRE(act_ok(g) && act_ok(y) && act_ok(gy) && vec_ok(g) && vec_ok(y) && vec_ok(gy),
                 "bn_bwd_apply: bad tensors");
   EUNET_REQUIRE(mean && invstd && scale && shift && dbeta && dgamma, "bn_bwd_apply: null stats");
-  EUNET_REQUIRE(g->dtype == y->dtype && gy->dtype == y->dtype && g->c == y->c && gy->c == y->c,
-                "bn_bwd_apply: mismatch");
+  EUNET_REQUIRE(like(g, y) && like(gy, y), "bn_bwd_apply: mismatch");
   const long long P = (long long)y->n * y->h * y->w;
-  const int U = y->c / e16(y->dtype);
-  EUNET_REQUIRE(U <= 256, "bn_bwd_apply: at most 256 channel units (C <= 256 x %d)", e16(y->dtype));
+  const int U = y->c / elems16(y->dtype);
+  EUNET_REQUIRE(U <= 256, "bn_bwd_apply: at most 256 channel units (C <= 256 x %d)", elems16(y->dtype));
   const int bs = (256 / U) * U;
   const long long nb = (P * U + bs - 1) / bs;
   const unsigned gr = (unsigned)(nb < 4096 ? nb : 4096);
-  if (y->dtype == EUNET_BF16)
-    bn_bwd_apply_kernel<bf16_t, bf16_t><<<gr, bs, 0, (hipStream_t)stream>>>(
-        (const bf16_t*)g->ptr, g->ctot, g->coff, (const bf16_t*)y->ptr, y->ctot, y->coff, P, y->c, mean, invstd,
-        scale, shift, dbeta, dgamma, (bf16_t*)gy->ptr, gy->ctot, gy->coff);
-  else
-    bn_bwd_apply_kernel<float, float><<<gr, bs, 0, (hipStream_t)stream>>>(
-        (const float*)g->ptr, g->ctot, g->coff, (const float*)y->ptr, y->ctot, y->coff, P, y->c, mean, invstd,
-        scale, shift, dbeta, dgamma, (float*)gy->ptr, gy->ctot, gy->coff);
+  by_dtype(y->dtype, [&](auto t) {
+    using T = decltype(t);
+    bn_bwd_apply_kernel<T, T><<<gr, bs, 0, (hipStream_t)stream>>>(
+        act_ptr<const T>(g), g->ctot, g->coff, act_ptr<const T>(y), y->ctot, y->coff, P, y->c, mean, invstd, scale,
+        shift, dbeta, dgamma, act_ptr<T>(gy), gy->ctot, gy->coff);
+  });
   EUNET_LAUNCH_CHECK("bn_bwd_apply");
   return EUNET_OK;
 }
@@ -1769,54 +1796,37 @@ int eunet_bn_bwd_apply_1x1(const eunet_act* y, const float* w, int k, const floa
   EUNET_REQUIRE(act_ok(y) && act_ok(gy) && vec_ok(y) && vec_ok(gy) && w && gz && mean && invstd && scale && shift &&
                     dbeta && dgamma,
                 "bn_bwd_apply_1x1: bad args");
-  EUNET_REQUIRE(k >= 1 && k <= 3 && gy->dtype == y->dtype && gy->c == y->c && gy->n == y->n && gy->h == y->h &&
-                    gy->w == y->w,
-                "bn_bwd_apply_1x1: K <= 3, gy like y");
+  EUNET_REQUIRE(k >= 1 && k <= 3 && like(gy, y), "bn_bwd_apply_1x1: K <= 3, gy like y");
   const long long P = (long long)y->n * y->h * y->w;
-  const int U = y->c / e16(y->dtype);
+  const int U = y->c / elems16(y->dtype);
   EUNET_REQUIRE(U <= 256, "bn_bwd_apply_1x1: at most 256 channel units");
   const int bs = (256 / U) * U;
   const long long nb = (P * U + bs - 1) / bs;
   const unsigned gr = (unsigned)(nb < 4096 ? nb : 4096);
-  if (y->dtype == EUNET_BF16)
-    bn_bwd_apply_1x1_kernel<bf16_t><<<gr, bs, 0, (hipStream_t)stream>>>(
-        (const bf16_t*)y->ptr, y->ctot, y->coff, P, y->c, w, k, gz, mean, invstd, scale, shift, dbeta, dgamma,
-        (bf16_t*)gy->ptr, gy->ctot, gy->coff);
-  else
-    bn_bwd_apply_1x1_kernel<float><<<gr, bs, 0, (hipStream_t)stream>>>(
-        (const float*)y->ptr, y->ctot, y->coff, P, y->c, w, k, gz, mean, invstd, scale, shift, dbeta, dgamma,
-        (float*)gy->ptr, gy->ctot, gy->coff);
+  by_dtype(y->dtype, [&](auto t) {
+    using T = decltype(t);
+    bn_bwd_apply_1x1_kernel<T><<<gr, bs, 0, (hipStream_t)stream>>>(act_ptr<const T>(y), y->ctot, y->coff, P, y->c, w, k,
+                                                                 gz, mean, invstd, scale, shift, dbeta, dgamma,
+                                                                 act_ptr<T>(gy), gy->ctot, gy->coff);
+  });
   EUNET_LAUNCH_CHECK("bn_bwd_apply_1x1");
   return EUNET_OK;
 }
 
 int eunet_pool_bwd_add(const eunet_act* act, const eunet_act* gpool, const eunet_act* gskip, const eunet_act* gout,
                        void* stream) {
-  EUNET_REQUIRE(act_ok(act) && act_ok(gpool) && act_ok(gout) && vec_ok(act) && vec_ok(gpool) && vec_ok(gout),
-                "pool_bwd_add: bad tensors");
-  if (gskip) EUNET_REQUIRE(act_ok(gskip) && vec_ok(gskip) && gskip->c == act->c, "pool_bwd_add: gskip");
-  EUNET_REQUIRE(gpool->h * 2 == act->h && gpool->w * 2 == act->w && gout->h == act->h && gout->w == act->w &&
-                    gpool->c == act->c && gout->c == act->c,
-                "pool_bwd_add: shapes");
-  const int E = e16(act->dtype);
-  const long long total = (long long)act->n * (act->h / 2) * (act->w / 2) * (act->c / E);
-  const unsigned gr = (unsigned)((total + 255) / 256);
-#define PBA(T)                                                                                                  \
-  pool_bwd_add_kernel<T><<<gr, 256, 0, (hipStream_t)stream>>>(                                                  \
-      (const T*)act->ptr, act->ctot, act->coff, (const T*)gpool->ptr, gpool->ctot, gpool->coff,                 \
-      gskip ? (const T*)gskip->ptr : nullptr, gskip ? gskip->ctot : 0, gskip ? gskip->coff : 0, (T*)gout->ptr, \
-      gout->ctot, gout->coff, act->n, act->h, act->w, act->c, BnRed{})
-  if (act->dtype == EUNET_BF16) PBA(bf16_t);
-  else PBA(float);
-#undef PBA
+  EUNET_REQUIRE(act_ok(act) && vec_ok(act) && act_ok(gout) && vec_ok(gout), "pool_bwd_add: bad tensors");
+  EUNET_REQUIRE(pool_bwd_inputs_ok(act, gpool, gskip) && like(gout, act),
+                "pool_bwd_add: gpool must be act's half, gskip and gout like act");
+  const long long total = (long long)act->n * (act->h / 2) * (act->w / 2) * (act->c / elems16(act->dtype));
+  pool_bwd_add_launch<false>(act, gpool, gskip, gout, BnRed{}, (unsigned)((total + 255) / 256), 256, stream);
   EUNET_LAUNCH_CHECK("pool_bwd_add");
   return EUNET_OK;
 }
 
 int eunet_upsample_bwd(const eunet_act* ghi, const eunet_act* glo, void* stream) {
   EUNET_REQUIRE(act_ok(ghi) && act_ok(glo), "upsample_bwd: bad tensors");
-  EUNET_REQUIRE(ghi->h == 2 * glo->h && ghi->w == 2 * glo->w && ghi->c == glo->c && ghi->n == glo->n,
-                "upsample_bwd: shapes");
+  EUNET_REQUIRE(is_2x(ghi, glo) && ghi->c == glo->c, "upsample_bwd: shapes");
   if (ghi->dtype == EUNET_F32 && glo->dtype == EUNET_F32 && ghi->ctot == ghi->c && glo->ctot == glo->c &&
       ghi->c <= 4 && ghi->coff == 0 && glo->coff == 0) {
     const long long total = (long long)glo->n * glo->h * glo->w;
@@ -1829,47 +1839,13 @@ int eunet_upsample_bwd(const eunet_act* ghi, const eunet_act* glo, void* stream)
     EUNET_LAUNCH_CHECK("upsample_bwd_small");
     return EUNET_OK;
   }
-  EUNET_REQUIRE(vec_ok(ghi) && vec_ok(glo) && ghi->dtype == glo->dtype, "upsample_bwd: vector layout");
-  const int E = e16(ghi->dtype);
-  const long long total = (long long)glo->n * ((glo->h + UP_R - 1) / UP_R) * ((glo->w + 1) / 2) * (glo->c / E);
-  const unsigned gr = (unsigned)((total + 255) / 256);
-  if (ghi->dtype == EUNET_BF16)
-    up_bwd_rows_kernel<bf16_t, bf16_t><<<gr, 256, 0, (hipStream_t)stream>>>(
-        (const bf16_t*)ghi->ptr, ghi->ctot, ghi->coff, (bf16_t*)glo->ptr, glo->ctot, glo->coff, glo->n, glo->h,
-        glo->w, glo->c, BnRed{});
-  else
-    up_bwd_rows_kernel<float, float><<<gr, 256, 0, (hipStream_t)stream>>>(
-        (const float*)ghi->ptr, ghi->ctot, ghi->coff, (float*)glo->ptr, glo->ctot, glo->coff, glo->n, glo->h,
-        glo->w, glo->c, BnRed{});
+  EUNET_REQUIRE(vec_ok(ghi) && vec_ok(glo) && same_dtype(ghi, glo), "upsample_bwd: vector layout");
+  up_bwd_rows_launch<false>(ghi, glo, BnRed{}, (unsigned)((up_threads(glo) + 255) / 256), 256, stream);
   EUNET_LAUNCH_CHECK("upsample_bwd");
   return EUNET_OK;
 }
 
 // ---- gradient producers with the BN-backward reduction of the block they feed fused in ----
-namespace {
-// block size of the fused BN-backward reductions: the block's threads must cover whole channel units
-// (a thread's unit is fixed across the grid-stride loop) -- 256 threads, or 192 for the channel counts
-// of base 96 (96 / 192 / 384 / 768 channels: 12 / 24 / 48 / 96 bf16 units); 0: not fusable
-int bnr_block(const eunet_act* g) {
-  const int U = g->c / e16(g->dtype);
-  return U > 0 && NT % U == 0 ? NT : (U > 0 && 192 % U == 0 ? 192 : 0);
-}
-bool bnr_ok(const eunet_act* g, const eunet_act* y) {
-  return act_ok(y) && vec_ok(y) && y->dtype == g->dtype && y->n == g->n && y->h == g->h && y->w == g->w &&
-         y->c == g->c && bnr_block(g) > 0;
-}
-long long pool_threads(const eunet_act* gout) {
-  return (long long)gout->n * (gout->h / 2) * (gout->w / 2) * (gout->c / e16(gout->dtype));
-}
-// fused-reduction grid, which is also the number of partial rows: at most cap blocks (each thread
-// then covers several outputs).  Measured: the max-pool adjoint prefers 2048 (fewer rows to write
-// and sum), the upsample adjoint, with more work per output, 8192 (more loads in flight).
-int bnr_grid(long long threads, int cap, int block) { return (int)std::min<long long>((threads + block - 1) / block, cap); }
-long long up_threads(const eunet_act* glo) {
-  return (long long)glo->n * ((glo->h + UP_R - 1) / UP_R) * ((glo->w + 1) / 2) * (glo->c / e16(glo->dtype));
-}
-}  // namespace
-
 int eunet_pool_bwd_add_bnr_rows(const eunet_act* gout, int* rows) {
   EUNET_REQUIRE(act_ok(gout) && rows, "pool_bwd_add_bnr_rows: bad args");
   const int bs = bnr_block(gout);
@@ -1881,33 +1857,17 @@ int eunet_pool_bwd_add_bnr(const eunet_act* act, const eunet_act* gpool, const e
                            const eunet_act* gout, const eunet_act* y, const float* mean, const float* invstd,
                            const float* scale, const float* shift, float* part, void* stream) {
   EUNET_REQUIRE(act_ok(act) && vec_ok(act), "pool_bwd_add_bnr: bad act");
-  eunet_act none;
-  if (!gout) {  // reduce only (the apply recomputes gout: eunet_bn_bwd_apply_pool)
-    none = *act;
-    none.ptr = nullptr;
-    none.ctot = act->c;
-    none.coff = 0;
-    gout = &none;
-  }
-  EUNET_REQUIRE(act_ok(gpool) && vec_ok(gpool) && (!gout->ptr || (act_ok(gout) && vec_ok(gout))),
-                "pool_bwd_add_bnr: bad tensors");
-  if (gskip) EUNET_REQUIRE(act_ok(gskip) && vec_ok(gskip) && gskip->c == act->c, "pool_bwd_add_bnr: gskip");
-  EUNET_REQUIRE(gpool->h * 2 == act->h && gpool->w * 2 == act->w && gout->h == act->h && gout->w == act->w &&
-                    gpool->c == act->c && gout->c == act->c,
-                "pool_bwd_add_bnr: shapes");
+  eunet_act none = *act;  // a dense gout of act's shape with a null ptr
+  none.ptr = nullptr; none.ctot = act->c; none.coff = 0;
+  if (!gout) gout = &none;  // reduce only (the apply recomputes gout: eunet_bn_bwd_apply_pool)
+  EUNET_REQUIRE(!gout->ptr || (act_ok(gout) && vec_ok(gout)), "pool_bwd_add_bnr: bad tensors");
+  EUNET_REQUIRE(pool_bwd_inputs_ok(act, gpool, gskip) && like(gout, act),
+                "pool_bwd_add_bnr: gpool must be act's half, gskip and gout like act");
   EUNET_REQUIRE(bnr_ok(gout, y) && mean && invstd && scale && shift && part,
                 "pool_bwd_add_bnr: y / BN args (and 256 or 192 %% channel units == 0)");
   const BnRed br{y->ptr, y->ctot, y->coff, mean, invstd, scale, shift, part};
   const int bs = bnr_block(gout);
-  const unsigned gr = (unsigned)bnr_grid(pool_threads(gout), 2048, bs);
-#define PBA(T)                                                                                                  \
-  pool_bwd_add_kernel<T, true><<<gr, bs, 0, (hipStream_t)stream>>>(                                             \
-      (const T*)act->ptr, act->ctot, act->coff, (const T*)gpool->ptr, gpool->ctot, gpool->coff,                 \
-      gskip ? (const T*)gskip->ptr : nullptr, gskip ? gskip->ctot : 0, gskip ? gskip->coff : 0, (T*)gout->ptr, \
-      gout->ctot, gout->coff, act->n, act->h, act->w, act->c, br)
-  if (act->dtype == EUNET_BF16) PBA(bf16_t);
-  else PBA(float);
-#undef PBA
+  pool_bwd_add_launch<true>(act, gpool, gskip, gout, br, (unsigned)bnr_grid(pool_threads(gout), 2048, bs), bs, stream);
   EUNET_LAUNCH_CHECK("pool_bwd_add_bnr");
   return EUNET_OK;
 }
@@ -1915,28 +1875,21 @@ int eunet_pool_bwd_add_bnr(const eunet_act* act, const eunet_act* gpool, const e
 int eunet_bn_bwd_apply_pool(const eunet_act* gpool, const eunet_act* gskip, const eunet_act* y, const float* mean,
                             const float* invstd, const float* scale, const float* shift, const float* dbeta,
                             const float* dgamma, const eunet_act* gy, void* stream) {
-  EUNET_REQUIRE(act_ok(gpool) && vec_ok(gpool) && act_ok(y) && vec_ok(y) && act_ok(gy) && vec_ok(gy) && mean &&
-                    invstd && scale && shift && dbeta && dgamma,
+  EUNET_REQUIRE(act_ok(y) && vec_ok(y) && act_ok(gy) && vec_ok(gy) && mean && invstd && scale && shift && dbeta &&
+                    dgamma,
                 "bn_bwd_apply_pool: bad args");
-  if (gskip) EUNET_REQUIRE(act_ok(gskip) && vec_ok(gskip) && gskip->c == y->c && gskip->n == y->n &&
-                               gskip->h == y->h && gskip->w == y->w && gskip->dtype == y->dtype,
-                           "bn_bwd_apply_pool: gskip");
-  EUNET_REQUIRE(gpool->h * 2 == y->h && gpool->w * 2 == y->w && gpool->n == y->n && gpool->c == y->c &&
-                    gpool->dtype == y->dtype && gy->n == y->n && gy->h == y->h && gy->w == y->w && gy->c == y->c &&
-                    gy->dtype == y->dtype,
+  EUNET_REQUIRE(pool_bwd_inputs_ok(y, gpool, gskip) && like(gy, y),
                 "bn_bwd_apply_pool: shapes (even H and W: every pixel in a 2x2 window)");
   const int bs = bnr_block(y);
   EUNET_REQUIRE(bs > 0, "bn_bwd_apply_pool: 256 or 192 %% channel units == 0");
-  const long long th = pool_threads(y);
-  const unsigned gr = (unsigned)std::min<long long>((th + bs - 1) / bs, 8192);
-#define BAP(T)                                                                                                       \
-  bn_bwd_apply_pool_kernel<T><<<gr, bs, 0, (hipStream_t)stream>>>(                                                   \
-      (const T*)gpool->ptr, gpool->ctot, gpool->coff, gskip ? (const T*)gskip->ptr : nullptr, gskip ? gskip->ctot : 0, \
-      gskip ? gskip->coff : 0, (const T*)y->ptr, y->ctot, y->coff, mean, invstd, scale, shift, dbeta, dgamma,          \
-      (T*)gy->ptr, gy->ctot, gy->coff, y->n, y->h, y->w, y->c)
-  if (y->dtype == EUNET_BF16) BAP(bf16_t);
-  else BAP(float);
-#undef BAP
+  const unsigned gr = (unsigned)bnr_grid(pool_threads(y), 8192, bs);
+  by_dtype(y->dtype, [&](auto t) {
+    using T = decltype(t);
+    bn_bwd_apply_pool_kernel<T><<<gr, bs, 0, (hipStream_t)stream>>>(
+        act_ptr<const T>(gpool), gpool->ctot, gpool->coff, act_ptr<const T>(gskip), gskip ? gskip->ctot : 0,
+        gskip ? gskip->coff : 0, act_ptr<const T>(y), y->ctot, y->coff, mean, invstd, scale, shift, dbeta, dgamma,
+        act_ptr<T>(gy), gy->ctot, gy->coff, y->n, y->h, y->w, y->c);
+  });
   EUNET_LAUNCH_CHECK("bn_bwd_apply_pool");
   return EUNET_OK;
 }
@@ -1950,23 +1903,14 @@ int eunet_upsample_bwd_bnr_rows(const eunet_act* glo, int* rows) {
 
 int eunet_upsample_bwd_bnr(const eunet_act* ghi, const eunet_act* glo, const eunet_act* y, const float* mean,
                            const float* invstd, const float* scale, const float* shift, float* part, void* stream) {
-  EUNET_REQUIRE(act_ok(ghi) && act_ok(glo) && vec_ok(ghi) && vec_ok(glo) && ghi->dtype == glo->dtype,
+  EUNET_REQUIRE(act_ok(ghi) && act_ok(glo) && vec_ok(ghi) && vec_ok(glo) && same_dtype(ghi, glo),
                 "upsample_bwd_bnr: bad tensors");
-  EUNET_REQUIRE(ghi->h == 2 * glo->h && ghi->w == 2 * glo->w && ghi->c == glo->c && ghi->n == glo->n,
-                "upsample_bwd_bnr: shapes");
+  EUNET_REQUIRE(is_2x(ghi, glo) && ghi->c == glo->c, "upsample_bwd_bnr: shapes");
   EUNET_REQUIRE(bnr_ok(glo, y) && mean && invstd && scale && shift && part,
                 "upsample_bwd_bnr: y / BN args (and 256 or 192 %% channel units == 0)");
   const BnRed br{y->ptr, y->ctot, y->coff, mean, invstd, scale, shift, part};
   const int bs = bnr_block(glo);
-  const unsigned gr = (unsigned)bnr_grid(up_threads(glo), 8192, bs);
-  if (ghi->dtype == EUNET_BF16)
-    up_bwd_rows_kernel<bf16_t, bf16_t, true><<<gr, bs, 0, (hipStream_t)stream>>>(
-        (const bf16_t*)ghi->ptr, ghi->ctot, ghi->coff, (bf16_t*)glo->ptr, glo->ctot, glo->coff, glo->n, glo->h,
-        glo->w, glo->c, br);
-  else
-    up_bwd_rows_kernel<float, float, true><<<gr, bs, 0, (hipStream_t)stream>>>(
-        (const float*)ghi->ptr, ghi->ctot, ghi->coff, (float*)glo->ptr, glo->ctot, glo->coff, glo->n, glo->h,
-        glo->w, glo->c, br);
+  up_bwd_rows_launch<true>(ghi, glo, br, (unsigned)bnr_grid(up_threads(glo), 8192, bs), bs, stream);
   EUNET_LAUNCH_CHECK("upsample_bwd_bnr");
   return EUNET_OK;
 }
@@ -1981,20 +1925,9 @@ int eunet_conv1x1_bwd(const eunet_act* y, const float* scale, const float* shift
                       const float* gz, const eunet_act* gact, float* part, void* stream) {
   EUNET_REQUIRE(act_ok(y) && act_ok(gact) && vec_ok(y) && vec_ok(gact) && scale && shift && w && gz && part,
                 "conv1x1_bwd: bad args");
-  EUNET_REQUIRE(k >= 1 && k <= 3 && y->c <= 128 && y->c % 8 == 0 && gact->c == y->c && gact->dtype == y->dtype,
-                "conv1x1_bwd: K<=3, C<=128, C%8==0");
-  const long long P = (long long)y->n * y->h * y->w;
-  const unsigned tiles = (unsigned)((P + C1X_PIX - 1) / C1X_PIX);
-  if (y->dtype == EUNET_BF16)
-    C1X_LAUNCH(conv1x1_bwd_kernel, bf16_t, false, ((const bf16_t*)y->ptr, P, y->c, y->ctot,
-                                                                        y->coff, scale, shift, w, k, gz,
-                                                                        (bf16_t*)gact->ptr, gact->ctot, gact->coff,
-                                                                        part, nullptr, nullptr, nullptr));
-  else
-    C1X_LAUNCH(conv1x1_bwd_kernel, float, false, ((const float*)y->ptr, P, y->c, y->ctot,
-                                                                       y->coff, scale, shift, w, k, gz,
-                                                                       (float*)gact->ptr, gact->ctot, gact->coff,
-                                                                       part, nullptr, nullptr, nullptr));
+  EUNET_REQUIRE(k >= 1 && k <= 3 && y->c <= 128 && y->c % 8 == 0 && like(gact, y),
+                "conv1x1_bwd: K<=3, C<=128, C%8==0, gact like y");
+  conv1x1_bwd_launch<false>(y, scale, shift, w, k, gz, gact, part, nullptr, nullptr, nullptr, stream);
   EUNET_LAUNCH_CHECK("conv1x1_bwd");
   return EUNET_OK;
 }
@@ -2005,24 +1938,11 @@ int eunet_conv1x1_bwd_bnr(const eunet_act* y, const float* scale, const float* s
   EUNET_REQUIRE(act_ok(y) && vec_ok(y) && (!gact || (act_ok(gact) && vec_ok(gact))) && scale && shift && w && gz &&
                     part,
                 "conv1x1_bwd: bad args");
-  EUNET_REQUIRE(k >= 1 && k <= 3 && y->c <= 128 && y->c % 8 == 0 &&
-                    (!gact || (gact->c == y->c && gact->dtype == y->dtype)),
-                "conv1x1_bwd: K<=3, C<=128, C%8==0");
-  const eunet_act none{};
-  if (!gact) gact = &none;  // (a null ptr: the kernel reduces without storing)
+  EUNET_REQUIRE(k >= 1 && k <= 3 && y->c <= 128 && y->c % 8 == 0 && (!gact || like(gact, y)),
+                "conv1x1_bwd: K<=3, C<=128, C%8==0, gact like y");
   EUNET_REQUIRE(mean && invstd && bn_part, "conv1x1_bwd_bnr: BN args");
-  const long long P = (long long)y->n * y->h * y->w;
-  const unsigned tiles = (unsigned)((P + C1X_PIX - 1) / C1X_PIX);
-  if (y->dtype == EUNET_BF16)
-    C1X_LAUNCH(conv1x1_bwd_kernel, bf16_t, true, ((const bf16_t*)y->ptr, P, y->c, y->ctot,
-                                                                        y->coff, scale, shift, w, k, gz,
-                                                                        (bf16_t*)gact->ptr, gact->ctot, gact->coff,
-                                                                        part, mean, invstd, bn_part));
-  else
-    C1X_LAUNCH(conv1x1_bwd_kernel, float, true, ((const float*)y->ptr, P, y->c, y->ctot,
-                                                                       y->coff, scale, shift, w, k, gz,
-                                                                       (float*)gact->ptr, gact->ctot, gact->coff,
-                                                                       part, mean, invstd, bn_part));
+  // (a null gact: the kernel reduces without storing)
+  conv1x1_bwd_launch<true>(y, scale, shift, w, k, gz, gact, part, mean, invstd, bn_part, stream);
   EUNET_LAUNCH_CHECK("conv1x1_bwd_bnr");
   return EUNET_OK;
 }

@@ -103,15 +103,14 @@ int eunet_debug_selftest(void* stream) {
 }
 
 int eunet_nchw_to_nhwc(const float* x, const eunet_act* out, void* stream) {
-  EUNET_REQUIRE(x && out && out->ptr && out->c > 0 && out->coff + out->c <= out->ctot, "nchw_to_nhwc: bad args");
+  EUNET_REQUIRE(x && act_ok(out), "nchw_to_nhwc: bad args");
   const long long total = (long long)out->n * out->c * out->h * out->w;
   const unsigned g = (unsigned)((total + 255) / 256);
-  if (out->dtype == EUNET_BF16)
-    nchw_to_nhwc_kernel<bf16_t><<<g, 256, 0, (hipStream_t)stream>>>(x, out->n, out->c, out->h, out->w,
-                                                                     (bf16_t*)out->ptr, out->ctot, out->coff);
-  else
-    nchw_to_nhwc_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>(x, out->n, out->c, out->h, out->w,
-                                                                    (float*)out->ptr, out->ctot, out->coff);
+  by_dtype(out->dtype, [&](auto t) {
+    using T = decltype(t);
+    nchw_to_nhwc_kernel<T><<<g, 256, 0, (hipStream_t)stream>>>(x, out->n, out->c, out->h, out->w, act_ptr<T>(out),
+                                                             out->ctot, out->coff);
+  });
   EUNET_LAUNCH_CHECK("nchw_to_nhwc");
   return EUNET_OK;
 }

@@ -264,6 +264,42 @@ inline void allow_lds(K* kernel, size_t bytes) {
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// ---------------------------------------------------------------------------
+// the activation-view contract of the C ABI (include/eunet.h, "activation views"), host side.
+// A launcher validates every view with act_ok (and vec_ok where its kernel moves 16-byte channel
+// units), states how its views agree with its reference view with the relations below, and writes
+// its launch once inside by_dtype.
+// ---------------------------------------------------------------------------
+inline bool act_ok(const eunet_act* a) {
+  return a && a->ptr && a->n > 0 && a->h > 0 && a->w > 0 && a->c > 0 && a->coff >= 0 &&
+         a->coff + a->c <= a->ctot && (a->dtype == EUNET_F32 || a->dtype == EUNET_BF16);
+}
+inline bool dtype_ok(int dtype) { return dtype == EUNET_F32 || dtype == EUNET_BF16; }
+// elements per 16-byte channel unit
+inline int elems16(int dtype) { return dtype == EUNET_BF16 ? 8 : 4; }
+// channels, row stride and slot are whole units of E elements (the view's own 16-byte unit by default)
+inline bool vec_ok(const eunet_act* a, int E) { return a->c % E == 0 && a->ctot % E == 0 && a->coff % E == 0; }
+inline bool vec_ok(const eunet_act* a) { return vec_ok(a, elems16(a->dtype)); }
+inline bool same_dtype(const eunet_act* a, const eunet_act* b) { return a->dtype == b->dtype; }
+inline bool same_nhw(const eunet_act* a, const eunet_act* b) { return a->n == b->n && a->h == b->h && a->w == b->w; }
+inline bool same_shape(const eunet_act* a, const eunet_act* b) { return same_nhw(a, b) && a->c == b->c; }
+// hi is the 2x of lo (pool, upsample, upconv)
+inline bool is_2x(const eunet_act* hi, const eunet_act* lo) {
+  return hi->n == lo->n && hi->h == 2 * lo->h && hi->w == 2 * lo->w;
+}
+// a view of the reference view's dtype, n, h, w and c: what most second operands must be
+inline bool like(const eunet_act* a, const eunet_act* ref) { return same_dtype(a, ref) && same_shape(a, ref); }
+
+// f(T{}) with T = the storage type of dtype (validated before: act_ok / dtype_ok)
+template <class F>
+inline void by_dtype(int dtype, F&& f) {
+  if (dtype == EUNET_BF16) f(bf16_t{});
+  else f(float{});
+}
+// the typed base pointer of a view; null for an absent (optional) view
+template <class T>
+inline T* act_ptr(const eunet_act* a) { return a ? (T*)a->ptr : nullptr; }
+
 // activation view accessors
 __host__ __device__ inline long long act_pix(const eunet_act& a, int n, int y, int x) {
   return ((long long)(n * a.h + y) * a.w + x);

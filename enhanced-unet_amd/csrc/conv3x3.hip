@@ -1391,13 +1391,23 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* part, co
   }
 }
 
-bool act_ok(const eunet_act* a) {
-  return a && a->ptr && a->n > 0 && a->h > 0 && a->w > 0 && a->c > 0 && a->coff >= 0 &&
-         a->coff + a->c <= a->ctot && (a->dtype == EUNET_F32 || a->dtype == EUNET_BF16);
-}
-
-int elems16(int dtype) { return dtype == EUNET_BF16 ? 8 : 4; }
 int kchunk(int dtype) { return 4 * elems16(dtype); }
+
+// the part of FwdArgs every pass through conv3x3_fwd_kernel shares: x = the operand view, y = the output view,
+// no input affine, bias, statistics, BN-backward fusion or gradient scale (the entry points set what they use)
+FwdArgs fwd_args(const eunet_act* x, const void* wp, const eunet_act* y) {
+  FwdArgs a;
+  a.x = x->ptr; a.N = x->n; a.H = x->h; a.W = x->w; a.xct = x->ctot; a.xco = x->coff; a.cin = x->c;
+  a.isc = nullptr; a.ish = nullptr; a.iss = 0;
+  a.wp = wp; a.cout_pad = cdiv(y->c, BN) * BN; a.nkc = cdiv(x->c, kchunk(x->dtype));
+  a.bias = nullptr;
+  a.y = y->ptr; a.yct = y->ctot; a.yco = y->coff; a.cout = y->c;
+  a.stats = nullptr; a.tx = cdiv(x->w, FTW); a.ty = cdiv(x->h, FTH); a.ntiles = x->n * a.tx * a.ty;
+  a.by = nullptr; a.byct = 0; a.byco = 0;
+  a.bmean = a.bistd = a.bsc = a.bsh = nullptr; a.bpart = nullptr; a.gsc = nullptr;
+  a.pro1 = 1;
+  return a;
+}
 
 template <bool DG>
 int launch_fwd(const FwdArgs& a, int dtype, void* stream, bool out_f32 = false) {
@@ -1440,30 +1450,31 @@ int launch_fwd(const FwdArgs& a, int dtype, void* stream, bool out_f32 = false) 
 extern "C" {
 
 int eunet_conv3x3_packed_bytes(int cout, int cin, int dtype, size_t* bytes) {
-  EUNET_REQUIRE(bytes && cout > 0 && cin > 0, "conv3x3_packed_bytes: bad args");
+  EUNET_REQUIRE(bytes && cout > 0 && cin > 0 && dtype_ok(dtype), "conv3x3_packed_bytes: bad args");
   const int cp = cdiv(cout, BN) * BN, kp = cdiv(cin, kchunk(dtype)) * kchunk(dtype);
   *bytes = (size_t)cp * kp * 9 * (dtype == EUNET_BF16 ? 2 : 4);
   return EUNET_OK;
 }
 
 int eunet_conv3x3_pack(const float* w, int cout, int cin, int flip, void* wp, int dtype, void* stream) {
-  EUNET_REQUIRE(w && wp && cout > 0 && cin > 0, "conv3x3_pack: bad args");
+  EUNET_REQUIRE(w && wp && cout > 0 && cin > 0 && dtype_ok(dtype), "conv3x3_pack: bad args");
   const int go = flip ? cin : cout, gi = flip ? cout : cin;  // GEMM output / input channels
   const int cp = cdiv(go, BN) * BN, kp = cdiv(gi, kchunk(dtype)) * kchunk(dtype);
   const long long total = (long long)cp * kp * 9;
   dim3 grid((unsigned)((total + 255) / 256));
-  if (dtype == EUNET_BF16)
-    pack_kernel<bf16_t><<<grid, 256, 0, (hipStream_t)stream>>>(w, cout, cin, flip, (bf16_t*)wp, cp, kp);
-  else
-    pack_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(w, cout, cin, flip, (float*)wp, cp, kp);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    pack_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>(w, cout, cin, flip, (T*)wp, cp, kp);
+  });
   EUNET_LAUNCH_CHECK("conv3x3_pack");
   return EUNET_OK;
 }
 
 int eunet_conv3x3_pack_many(const eunet_pack_desc* descs, int n, int dtype, void* stream) {
   EUNET_REQUIRE(descs && n > 0 && n <= EUNET_PACK_MAX, "conv3x3_pack_many: 1..%d tensors", EUNET_PACK_MAX);
+  EUNET_REQUIRE(dtype_ok(dtype), "conv3x3_pack_many: bad dtype %d", dtype);
   PackBatch b;
-  const int E = dtype == EUNET_BF16 ? 8 : 4;
+  const int E = elems16(dtype);
   long long blocks = 0;
   for (int i = 0; i < n; ++i) {
     const eunet_pack_desc& d = descs[i];
@@ -1479,8 +1490,7 @@ int eunet_conv3x3_pack_many(const eunet_pack_desc* descs, int n, int dtype, void
   EUNET_REQUIRE(blocks < (1ll << 31), "conv3x3_pack_many: too large");
   b.bstart[n] = (int)blocks;
   b.n = n;
-  if (dtype == EUNET_BF16) pack_many_kernel<bf16_t><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(b);
-  else pack_many_kernel<float><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(b);
+  by_dtype(dtype, [&](auto t) { pack_many_kernel<decltype(t)><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(b); });
   EUNET_LAUNCH_CHECK("conv3x3_pack_many");
   return EUNET_OK;
 }
@@ -1494,25 +1504,16 @@ int eunet_conv3x3_tiles(const eunet_act* y, int* tiles) {
 int eunet_conv3x3_fwd(const eunet_act* x, const float* in_scale, const float* in_shift, int in_nstride,
                       const void* wp, const float* bias, const eunet_act* y, float* stats, void* stream) {
   EUNET_REQUIRE(act_ok(x) && act_ok(y) && wp, "conv3x3_fwd: bad tensors");
-  EUNET_REQUIRE(x->dtype == y->dtype, "conv3x3_fwd: dtype mismatch");
-  EUNET_REQUIRE(x->n == y->n && x->h == y->h && x->w == y->w, "conv3x3_fwd: spatial mismatch");
-  const int E = elems16(x->dtype);
-  EUNET_REQUIRE(x->c % E == 0 && x->ctot % E == 0 && x->coff % E == 0,
-                "conv3x3_fwd: input channels/stride/offset must be multiples of %d", E);
+  EUNET_REQUIRE(same_dtype(x, y), "conv3x3_fwd: dtype mismatch");
+  EUNET_REQUIRE(same_nhw(x, y), "conv3x3_fwd: spatial mismatch");
+  EUNET_REQUIRE(vec_ok(x) && vec_ok(y), "conv3x3_fwd: channels/strides/offsets must be multiples of %d",
+                elems16(x->dtype));
   EUNET_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv3x3_fwd: scale/shift pair");
-  FwdArgs a;
-  a.x = x->ptr; a.N = x->n; a.H = x->h; a.W = x->w; a.xct = x->ctot; a.xco = x->coff; a.cin = x->c;
   EUNET_REQUIRE(in_nstride == 0 || (in_scale && in_nstride >= x->c), "conv3x3_fwd: in_nstride");
+  FwdArgs a = fwd_args(x, wp, y);
   a.isc = in_scale; a.ish = in_shift; a.iss = in_nstride;
-  a.wp = wp; a.cout_pad = cdiv(y->c, BN) * BN; a.nkc = cdiv(x->c, kchunk(x->dtype));
   a.bias = bias;
-  a.y = y->ptr; a.yct = y->ctot; a.yco = y->coff; a.cout = y->c;
-  a.stats = stats; a.tx = cdiv(x->w, FTW); a.ty = cdiv(x->h, FTH); a.ntiles = x->n * a.tx * a.ty;
-  a.by = nullptr; a.byct = 0; a.byco = 0;
-  a.bmean = a.bistd = a.bsc = a.bsh = nullptr; a.bpart = nullptr; a.gsc = nullptr;
-  a.pro1 = 1;
-  EUNET_REQUIRE(y->c % E == 0 && y->ctot % E == 0 && y->coff % E == 0,
-                "conv3x3_fwd: output channels/stride/offset must be multiples of %d", E);
+  a.stats = stats;
   return launch_fwd<false>(a, x->dtype, stream);
 }
 
@@ -1521,22 +1522,12 @@ int eunet_conv3x3_dgrad(const eunet_act* dy, const void* wp_t, const eunet_act* 
   EUNET_REQUIRE(act_ok(dy) && act_ok(gx) && wp_t, "conv3x3_dgrad: bad args");
   // gx is dy's dtype, or fp32 for a bf16 dy (the output rounded to fp32 instead of bf16)
   const bool out_f32 = dy->dtype == EUNET_BF16 && gx->dtype == EUNET_F32;
-  EUNET_REQUIRE(dy->dtype == gx->dtype || out_f32, "conv3x3_dgrad: dtype mismatch");
-  EUNET_REQUIRE(dy->n == gx->n && dy->h == gx->h && dy->w == gx->w, "conv3x3_dgrad: spatial mismatch");
-  const int E = elems16(dy->dtype);
-  EUNET_REQUIRE(dy->c % E == 0 && dy->ctot % E == 0 && dy->coff % E == 0 && gx->c % E == 0 && gx->ctot % E == 0 &&
-                    gx->coff % E == 0,
-                "conv3x3_dgrad: channels/strides must be multiples of %d", E);
-  FwdArgs a;
-  a.x = dy->ptr; a.N = dy->n; a.H = dy->h; a.W = dy->w; a.xct = dy->ctot; a.xco = dy->coff; a.cin = dy->c;
-  a.isc = nullptr; a.ish = nullptr; a.iss = 0;
-  a.wp = wp_t; a.cout_pad = cdiv(gx->c, BN) * BN; a.nkc = cdiv(dy->c, kchunk(dy->dtype));
-  a.bias = nullptr;
-  a.y = gx->ptr; a.yct = gx->ctot; a.yco = gx->coff; a.cout = gx->c;
-  a.stats = nullptr; a.tx = cdiv(dy->w, FTW); a.ty = cdiv(dy->h, FTH); a.ntiles = dy->n * a.tx * a.ty;
-  a.by = nullptr; a.byct = 0; a.byco = 0;
-  a.bmean = a.bistd = a.bsc = a.bsh = nullptr; a.bpart = nullptr; a.gsc = gscale;
-  a.pro1 = 1;
+  EUNET_REQUIRE(same_dtype(dy, gx) || out_f32, "conv3x3_dgrad: dtype mismatch");
+  EUNET_REQUIRE(same_nhw(dy, gx), "conv3x3_dgrad: spatial mismatch");
+  const int E = elems16(dy->dtype);  // also of an fp32 gx behind a bf16 dy: the kernel's units are dy's
+  EUNET_REQUIRE(vec_ok(dy) && vec_ok(gx, E), "conv3x3_dgrad: channels/strides must be multiples of %d", E);
+  FwdArgs a = fwd_args(dy, wp_t, gx);
+  a.gsc = gscale;
   return launch_fwd<true>(a, dy->dtype, stream, out_f32);
 }
 
@@ -1545,24 +1536,13 @@ int eunet_conv3x3_dgrad_bnbwd(const eunet_act* dy, const void* wp_t, const eunet
                               const float* gscale, float* part, void* stream) {
   EUNET_REQUIRE(act_ok(dy) && act_ok(gx) && act_ok(y) && wp_t && mean && invstd && scale && shift && part,
                 "conv3x3_dgrad_bnbwd: bad args");
-  EUNET_REQUIRE(dy->dtype == gx->dtype && y->dtype == gx->dtype, "conv3x3_dgrad_bnbwd: dtype mismatch");
-  EUNET_REQUIRE(dy->n == gx->n && dy->h == gx->h && dy->w == gx->w && y->n == gx->n && y->h == gx->h &&
-                    y->w == gx->w && y->c == gx->c,
-                "conv3x3_dgrad_bnbwd: shape mismatch");
-  const int E = elems16(dy->dtype);
-  EUNET_REQUIRE(dy->c % E == 0 && dy->ctot % E == 0 && dy->coff % E == 0 && gx->c % E == 0 && gx->ctot % E == 0 &&
-                    gx->coff % E == 0 && y->ctot % E == 0 && y->coff % E == 0,
-                "conv3x3_dgrad_bnbwd: channels/strides must be multiples of %d", E);
-  FwdArgs a;
-  a.x = dy->ptr; a.N = dy->n; a.H = dy->h; a.W = dy->w; a.xct = dy->ctot; a.xco = dy->coff; a.cin = dy->c;
-  a.isc = nullptr; a.ish = nullptr; a.iss = 0;
-  a.wp = wp_t; a.cout_pad = cdiv(gx->c, BN) * BN; a.nkc = cdiv(dy->c, kchunk(dy->dtype));
-  a.bias = nullptr;
-  a.y = gx->ptr; a.yct = gx->ctot; a.yco = gx->coff; a.cout = gx->c;
-  a.stats = nullptr; a.tx = cdiv(dy->w, FTW); a.ty = cdiv(dy->h, FTH); a.ntiles = dy->n * a.tx * a.ty;
+  EUNET_REQUIRE(same_dtype(dy, gx) && same_dtype(y, gx), "conv3x3_dgrad_bnbwd: dtype mismatch");
+  EUNET_REQUIRE(same_nhw(dy, gx) && same_shape(y, gx), "conv3x3_dgrad_bnbwd: shape mismatch");
+  EUNET_REQUIRE(vec_ok(dy) && vec_ok(gx) && vec_ok(y), "conv3x3_dgrad_bnbwd: channels/strides must be multiples of %d",
+                elems16(dy->dtype));
+  FwdArgs a = fwd_args(dy, wp_t, gx);
   a.by = y->ptr; a.byct = y->ctot; a.byco = y->coff;
   a.bmean = mean; a.bistd = invstd; a.bsc = scale; a.bsh = shift; a.bpart = part; a.gsc = gscale;
-  a.pro1 = 1;
   return launch_fwd<true>(a, dy->dtype, stream);
 }
 
@@ -1610,12 +1590,10 @@ int eunet_conv_stamps(void* out, size_t bytes) {  // diagnostic builds only (too
 int eunet_conv3x3_wgrad(const eunet_act* x, const float* in_scale, const float* in_shift, int in_nstride,
                         const eunet_act* dy, float* dw_part, float* db_part, int nsplit, void* stream) {
   EUNET_REQUIRE(act_ok(x) && act_ok(dy) && dw_part && nsplit > 0, "conv3x3_wgrad: bad args");
-  EUNET_REQUIRE(x->dtype == dy->dtype, "conv3x3_wgrad: dtype mismatch");
-  EUNET_REQUIRE(x->n == dy->n && x->h == dy->h && x->w == dy->w, "conv3x3_wgrad: spatial mismatch");
-  const int E = elems16(x->dtype);
-  EUNET_REQUIRE(x->c % E == 0 && x->ctot % E == 0 && x->coff % E == 0 && dy->c % E == 0 &&
-                    dy->ctot % E == 0 && dy->coff % E == 0,
-                "conv3x3_wgrad: channels/strides must be multiples of %d", E);
+  EUNET_REQUIRE(same_dtype(x, dy), "conv3x3_wgrad: dtype mismatch");
+  EUNET_REQUIRE(same_nhw(x, dy), "conv3x3_wgrad: spatial mismatch");
+  EUNET_REQUIRE(vec_ok(x) && vec_ok(dy), "conv3x3_wgrad: channels/strides must be multiples of %d",
+                elems16(x->dtype));
   WgArgs a;
   a.x = x->ptr; a.N = x->n; a.H = x->h; a.W = x->w; a.xct = x->ctot; a.xco = x->coff; a.cin = x->c;
   EUNET_REQUIRE(in_nstride == 0 || (in_scale && in_nstride >= x->c), "conv3x3_wgrad: in_nstride");

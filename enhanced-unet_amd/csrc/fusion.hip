@@ -613,17 +613,15 @@ int eunet_gate_mid_fwd(const float* za, const float* zb, int n, int h, int w, in
 
 int eunet_gate_out_fwd(const float* za, const float* zb, int n, int h, int w, int k, const float* b,
                        const float* sc2, const float* sh2, const eunet_act* f2, void* stream) {
-  EUNET_REQUIRE(za && zb && b && sc2 && sh2 && f2 && f2->ptr && k >= 1 && k <= 3, "gate_out_fwd: bad args");
+  EUNET_REQUIRE(za && zb && b && sc2 && sh2 && act_ok(f2) && k >= 1 && k <= 3, "gate_out_fwd: bad args");
   EUNET_REQUIRE(f2->ctot == F2C && f2->coff == 0 && f2->c == 2 * k && f2->n == n && f2->h == h && f2->w == w,
                 "gate_out_fwd: f2 must be [n,h,w,8] with c = 2K");
   GateArgs g = gate_args(za, zb, n, h, w);
   const unsigned gr = grid_for(g.P);
-  if (f2->dtype == EUNET_BF16)
-    EUNET_K_DISPATCH(k, gate_out_fwd_kernel<KK, bf16_t><<<gr, NT, 0, (hipStream_t)stream>>>(g, b, sc2, sh2,
-                                                                                           (bf16_t*)f2->ptr));
-  else
-    EUNET_K_DISPATCH(k, gate_out_fwd_kernel<KK, float><<<gr, NT, 0, (hipStream_t)stream>>>(g, b, sc2, sh2,
-                                                                                          (float*)f2->ptr));
+  by_dtype(f2->dtype, [&](auto t) {
+    using T = decltype(t);
+    EUNET_K_DISPATCH(k, gate_out_fwd_kernel<KK, T><<<gr, NT, 0, (hipStream_t)stream>>>(g, b, sc2, sh2, act_ptr<T>(f2)));
+  });
   EUNET_LAUNCH_CHECK("gate_out_fwd");
   return EUNET_OK;
 }
@@ -631,18 +629,17 @@ int eunet_gate_out_fwd(const float* za, const float* zb, int n, int h, int w, in
 int eunet_fusion_out_fwd(const float* za, const float* zb, int k, const eunet_act* y3, const float* sc3,
                          const float* sh3, const float* w11, const float* b11, const float* b, const float* sc2,
                          const float* sh2, const float* wr, const float* br, float* out, void* stream) {
-  EUNET_REQUIRE(za && zb && y3 && y3->ptr && sc3 && sh3 && w11 && b11 && b && sc2 && sh2 && wr && br && out &&
-                    k >= 1 && k <= 3,
+  EUNET_REQUIRE(za && zb && act_ok(y3) && sc3 && sh3 && w11 && b11 && b && sc2 && sh2 && wr && br && out && k >= 1 &&
+                    k <= 3,
                 "fusion_out_fwd: bad args");
   EUNET_REQUIRE(y3->c == 64 && y3->ctot == 64 && y3->coff == 0, "fusion_out_fwd: y3 must be [n,h,w,64]");
   GateArgs g = gate_args(za, zb, y3->n, y3->h, y3->w);
   const unsigned gr = grid_for(g.P);
-  if (y3->dtype == EUNET_BF16)
-    EUNET_K_DISPATCH(k, fusion_out_fwd_kernel<KK, bf16_t><<<gr, NT, 0, (hipStream_t)stream>>>(
-                            g, (const bf16_t*)y3->ptr, sc3, sh3, w11, b11, b, sc2, sh2, wr, br, out));
-  else
-    EUNET_K_DISPATCH(k, fusion_out_fwd_kernel<KK, float><<<gr, NT, 0, (hipStream_t)stream>>>(
-                            g, (const float*)y3->ptr, sc3, sh3, w11, b11, b, sc2, sh2, wr, br, out));
+  by_dtype(y3->dtype, [&](auto t) {
+    using T = decltype(t);
+    EUNET_K_DISPATCH(k, fusion_out_fwd_kernel<KK, T><<<gr, NT, 0, (hipStream_t)stream>>>(
+                            g, act_ptr<const T>(y3), sc3, sh3, w11, b11, b, sc2, sh2, wr, br, out));
+  });
   EUNET_LAUNCH_CHECK("fusion_out_fwd");
   return EUNET_OK;
 }
@@ -662,17 +659,16 @@ int eunet_fusion_out_bwd(const float* za, const float* zb, int n, int h, int w, 
 int eunet_gate_bwd1(const float* za, const float* zb, int k, const eunet_act* gf2conv, const float* gf2res,
                     const float* b, const float* mean2, const float* istd2, const float* gam2, const float* bet2,
                     float* gffd, float* gbhat, float* part, void* stream) {
-  EUNET_REQUIRE(za && zb && gf2conv && gf2conv->ptr && gf2res && b && mean2 && istd2 && gam2 && bet2 && gffd &&
-                    gbhat && part && k >= 1 && k <= 3,
+  EUNET_REQUIRE(za && zb && act_ok(gf2conv) && gf2res && b && mean2 && istd2 && gam2 && bet2 && gffd && gbhat &&
+                    part && k >= 1 && k <= 3,
                 "gate_bwd1: bad args");
   EUNET_REQUIRE(gf2conv->ctot == F2C && gf2conv->coff == 0, "gate_bwd1: g_f2 must be [n,h,w,8]");
   GateArgs g = gate_args(za, zb, gf2conv->n, gf2conv->h, gf2conv->w);
-  if (gf2conv->dtype == EUNET_BF16)
-    EUNET_K_DISPATCH(k, gate_bwd1_kernel<KK, bf16_t><<<g.tiles, NT, 0, (hipStream_t)stream>>>(
-                            g, (const bf16_t*)gf2conv->ptr, gf2res, b, mean2, istd2, gam2, bet2, gffd, gbhat, part));
-  else
-    EUNET_K_DISPATCH(k, gate_bwd1_kernel<KK, float><<<g.tiles, NT, 0, (hipStream_t)stream>>>(
-                            g, (const float*)gf2conv->ptr, gf2res, b, mean2, istd2, gam2, bet2, gffd, gbhat, part));
+  by_dtype(gf2conv->dtype, [&](auto t) {
+    using T = decltype(t);
+    EUNET_K_DISPATCH(k, gate_bwd1_kernel<KK, T><<<g.tiles, NT, 0, (hipStream_t)stream>>>(
+                            g, act_ptr<const T>(gf2conv), gf2res, b, mean2, istd2, gam2, bet2, gffd, gbhat, part));
+  });
   EUNET_LAUNCH_CHECK("gate_bwd1");
   return EUNET_OK;
 }

@@ -369,21 +369,15 @@ __global__ __launch_bounds__(256) void upconv_pack_kernel(const float* w, int C,
   Elem<T>::st(wp + total + e, v);
 }
 
-bool up_act_ok(const eunet_act* a) {
-  return a && a->ptr && a->n > 0 && a->h > 0 && a->w > 0 && a->c > 0 && a->coff >= 0 && a->coff + a->c <= a->ctot &&
-         (a->dtype == EUNET_F32 || a->dtype == EUNET_BF16);
-}
-
 // the checks every pass shares: lo = the low-res side (y or gd), hi = the 2x side (out or g)
 int up_check(const char* what, const eunet_act* lo, const eunet_act* hi) {
-  EUNET_REQUIRE(up_act_ok(lo) && up_act_ok(hi), "%s: bad tensors", what);
-  EUNET_REQUIRE(lo->dtype == hi->dtype, "%s: dtype mismatch", what);
+  EUNET_REQUIRE(act_ok(lo) && act_ok(hi), "%s: bad tensors", what);
+  EUNET_REQUIRE(same_dtype(lo, hi), "%s: dtype mismatch", what);
   EUNET_REQUIRE(lo->c == hi->c, "%s: the layer keeps its channel count (%d vs %d)", what, lo->c, hi->c);
   EUNET_REQUIRE(lo->c % 32 == 0, "%s: channels must be a multiple of 32 (got %d)", what, lo->c);
-  EUNET_REQUIRE(hi->n == lo->n && hi->h == 2 * lo->h && hi->w == 2 * lo->w, "%s: the output is 2h x 2w of the input", what);
-  const int E = lo->dtype == EUNET_BF16 ? 8 : 4;
-  EUNET_REQUIRE(lo->ctot % E == 0 && lo->coff % E == 0 && hi->ctot % E == 0 && hi->coff % E == 0,
-                "%s: channel strides/offsets must be multiples of %d", what, E);
+  EUNET_REQUIRE(is_2x(hi, lo), "%s: the output is 2h x 2w of the input", what);
+  EUNET_REQUIRE(vec_ok(lo) && vec_ok(hi), "%s: channel strides/offsets must be multiples of %d", what,
+                elems16(lo->dtype));
   EUNET_REQUIRE(((uintptr_t)lo->ptr & 15) == 0 && ((uintptr_t)hi->ptr & 15) == 0, "%s: tensors must be 16-byte aligned", what);
   EUNET_REQUIRE((long long)lo->n * lo->h * lo->w < (1ll << 31) - UT, "%s: too many pixels", what);
   return EUNET_OK;
@@ -392,10 +386,9 @@ int up_check(const char* what, const eunet_act* lo, const eunet_act* hi) {
 template <int MODE>
 int up_launch(const UpArgs& a, int dtype, long long blocks, const char* what, void* stream) {
   EUNET_REQUIRE(blocks > 0 && blocks < (1ll << 31), "%s: grid too large", what);
-  if (dtype == EUNET_BF16)
-    upconv_kernel<bf16_t, MODE><<<(unsigned)blocks, NT, 0, (hipStream_t)stream>>>(a);
-  else
-    upconv_kernel<float, MODE><<<(unsigned)blocks, NT, 0, (hipStream_t)stream>>>(a);
+  by_dtype(dtype, [&](auto t) {
+    upconv_kernel<decltype(t), MODE><<<(unsigned)blocks, NT, 0, (hipStream_t)stream>>>(a);
+  });
   return eunet::check_launch(what);
 }
 
@@ -415,19 +408,21 @@ int stage_k(int dtype) { return dtype == EUNET_BF16 ? 64 : 32; }  // BK of upcon
 extern "C" {
 
 int eunet_upconv2x2_packed_bytes(int c, int dtype, size_t* bytes) {
-  EUNET_REQUIRE(bytes && c > 0 && (dtype == EUNET_F32 || dtype == EUNET_BF16), "upconv2x2_packed_bytes: bad args");
+  EUNET_REQUIRE(bytes && c > 0 && dtype_ok(dtype), "upconv2x2_packed_bytes: bad args");
   *bytes = (size_t)8 * c * c * (dtype == EUNET_BF16 ? 2 : 4);
   return EUNET_OK;
 }
 
 int eunet_upconv2x2_pack(const float* w, int c, void* wp, int dtype, void* stream) {
-  EUNET_REQUIRE(w && wp && c > 0 && (dtype == EUNET_F32 || dtype == EUNET_BF16), "upconv2x2_pack: bad args");
+  EUNET_REQUIRE(w && wp && c > 0 && dtype_ok(dtype), "upconv2x2_pack: bad args");
   EUNET_REQUIRE(c % 32 == 0, "upconv2x2_pack: channels must be a multiple of 32 (got %d)", c);
   EUNET_REQUIRE(((uintptr_t)wp & 15) == 0, "upconv2x2_pack: packed operand not 16-byte aligned");
   const long long total = 4ll * c * c;
   const unsigned grid = (unsigned)((total + 255) / 256);
-  if (dtype == EUNET_BF16) upconv_pack_kernel<bf16_t><<<grid, 256, 0, (hipStream_t)stream>>>(w, c, (bf16_t*)wp);
-  else upconv_pack_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(w, c, (float*)wp);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    upconv_pack_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>(w, c, (T*)wp);
+  });
   EUNET_LAUNCH_CHECK("upconv2x2_pack");
   return EUNET_OK;
 }
@@ -460,7 +455,7 @@ int eunet_upconv2x2_dgrad(const eunet_act* g, const void* wp, const eunet_act* g
 }
 
 int eunet_upconv2x2_wgrad_splits(const eunet_act* y, int dtype, int* nsplit) {
-  EUNET_REQUIRE(up_act_ok(y) && nsplit && (dtype == EUNET_F32 || dtype == EUNET_BF16), "upconv2x2_wgrad_splits: bad args");
+  EUNET_REQUIRE(act_ok(y) && nsplit && dtype_ok(dtype), "upconv2x2_wgrad_splits: bad args");
   const long long M = (long long)y->n * y->h * y->w;
   const long long ktiles = (M + stage_k(dtype) - 1) / stage_k(dtype);
   const int blocks = cdiv(y->c, UT) * cdiv(4 * y->c, UT);

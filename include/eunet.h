@@ -33,7 +33,21 @@ extern "C" {
 
 enum { EUNET_F32 = 0, EUNET_BF16 = 1 };
 
-/* NHWC view: element (n,y,x,c) lives at ptr + ((n*h + y)*w + x)*ctot + coff + c */
+/* NHWC view: element (n,y,x,c) lives at ptr + ((n*h + y)*w + x)*ctot + coff + c
+ *
+ * The activation-view contract, checked by every entry point that takes views before it launches
+ * anything (a violation returns EUNET_ERR_INVALID and touches no memory):
+ *   - a valid view has a non-null ptr, n, h, w, c > 0, 0 <= coff, coff + c <= ctot and dtype EUNET_F32 or
+ *     EUNET_BF16 (any other code is refused, also where a function takes a bare dtype argument);
+ *   - the views of one call agree in dtype and n, and in h and w up to the factor 2 the op defines (pool,
+ *     upsample, upconv), optional (nullable) views included; where channels correspond, in c too.  The
+ *     exceptions are stated at the function (eunet_conv3x3_dgrad's fp32 gx, the small-K fp32 path of
+ *     eunet_upsample_bwd);
+ *   - the ops that move whole 16-byte channel units need c, ctot and coff to be multiples of the unit, 8
+ *     (bf16) or 4 (fp32) elements: eunet_conv3x3_*, eunet_conv_small_wgrad (dy), eunet_bnrelu*, the
+ *     eunet_bn_bwd_*, eunet_pool_bwd_*, eunet_upsample_bwd* (vector path) and eunet_conv1x1_bwd* families and
+ *     the eunet_*upconv2x2_* passes (which also need 16-byte aligned pointers).  eunet_nchw_to_nhwc,
+ *     eunet_conv_small_fwd and the fusion entry points take any channel layout their comment allows. */
 typedef struct {
   void* ptr;
   int n, h, w;  /* batch, rows, cols */
@@ -109,7 +123,9 @@ int eunet_conv3x3_dgrad_bnbwd(const eunet_act* dy, const void* wp_t, const eunet
                               const float* scale, const float* shift, const float* gscale,
                               float* part, void* stream);
 /* plain dgrad (autograd of models.py:219,222 w.r.t. the conv input): gx = conv(dy, W') with
- * wp_t packed transpose_flip; gscale (nullable) [N][gx.c] scales gx per sample and channel */
+ * wp_t packed transpose_flip; gscale (nullable) [N][gx.c] scales gx per sample and channel.  gx has dy's
+ * dtype, or (the one mixed-dtype call) fp32 for a bf16 dy: the output is then stored unrounded, and gx's
+ * c, ctot and coff are still multiples of dy's unit of 8 */
 int eunet_conv3x3_dgrad(const eunet_act* dy, const void* wp_t, const eunet_act* gx, const float* gscale,
                         void* stream);
 /* wgrad (split over pixel tiles): dw_part [nsplit][cout][9][cin] and
@@ -127,8 +143,7 @@ int eunet_wgrad_reduce(const float* dw_part, const float* db_part, int nsplit, i
 int eunet_conv_small_fwd(const eunet_act* x, const float* w, const float* bias,
                          const eunet_act* y, float* stats, void* stream);
 int eunet_conv_small_wgrad_splits(const eunet_act* dy, int* nsplit);
-/* dy is read in whole 16-byte units: dy->c, dy->ctot and dy->coff must be multiples of 8 (bf16) / 4
- * (fp32), and x and dy must agree in n, h, w; anything else is EUNET_ERR_INVALID */
+/* dy is read in whole 16-byte units (the view contract at eunet_act); x (Cin <= 8) may have any layout */
 int eunet_conv_small_wgrad(const eunet_act* x, const eunet_act* dy, float* dw_part,
                            float* db_part, int nsplit, void* stream);
 
@@ -356,7 +371,8 @@ int eunet_debug_selftest(void* stream);
  * saved activation) + the skip-path gradient: gout = gskip + scatter(gpool) */
 int eunet_pool_bwd_add(const eunet_act* act, const eunet_act* gpool, const eunet_act* gskip,
                        const eunet_act* gout, void* stream);
-/* Upsample x2 backward (adjoint of the bilinear taps) */
+/* Upsample x2 backward (adjoint of the bilinear taps).  Dense fp32 views (ctot == c, coff == 0) of c <= 4
+ * channels take a scalar path without the 16-byte unit requirement (the K-channel logits of the head) */
 int eunet_upsample_bwd(const eunet_act* ghi, const eunet_act* glo, void* stream);
 /* The two producers above with the reduction half of eunet_bn_bwd_reduce fused in: gout / glo is
  * the gradient w.r.t. relu(bn(y)) of the DoubleConv output y (models.py:222-223), and

@@ -270,6 +270,41 @@ def test_opt_table_layout_and_supported():
     assert not optim.supported(torch.optim.SGD([p], lr=0.1))
 
 
+# the non-launching queries of the C ABI that take an activation view: (symbol, arguments between the view and
+# the int result, result for the good view of test_view_queries_share_the_view_contract)
+VIEW_QUERIES = [("eunet_conv3x3_tiles", (), 18), ("eunet_bn_bwd_tiles", (), 120), ("eunet_conv1x1_bwd_tiles", (), 8),
+                ("eunet_pool_bwd_add_bnr_rows", (), 60), ("eunet_upsample_bwd_bnr_rows", (), 15),
+                ("eunet_conv_small_wgrad_splits", (), 36), ("eunet_conv3x3_wgrad_splits", (32, 1), 60),
+                ("eunet_upconv2x2_wgrad_splits", (1,), 120)]
+
+
+@pytest.mark.parametrize("name,mid,expect", VIEW_QUERIES, ids=[q[0] for q in VIEW_QUERIES])
+def test_view_queries_share_the_view_contract(name, mid, expect):
+    """Host-only (descriptors with a made-up pointer: these entry points launch nothing and dereference nothing).
+    Every query validates its view with the one act_ok of csrc/common.h: a null ptr, c = 0, coff + c > ctot,
+    coff < 0 and a dtype code that is neither EUNET_F32 nor EUNET_BF16 are EUNET_ERR_INVALID with the output
+    untouched; the good view [2, 48, 80] x channels 32..95 of 96, bf16, gives the value recorded from the
+    library before the launchers shared their checks."""
+    import ctypes
+    from eunet import _lib
+    lib = _lib.load()
+    assert _lib.EUNET_BF16 == 1
+
+    def query(ptr, c, ctot, coff, dtype):
+        view = _lib.Act(ptr, 2, 48, 80, c, ctot, coff, dtype)
+        out = ctypes.c_int(-7)
+        return getattr(lib, name)(ctypes.byref(view), *mid, ctypes.byref(out)), out.value
+
+    assert query(0x1000, 64, 96, 32, _lib.EUNET_BF16) == (0, expect)
+    for bad in [(None, 64, 96, 32, _lib.EUNET_BF16),    # null ptr
+                (0x1000, 0, 96, 32, _lib.EUNET_BF16),   # no channels
+                (0x1000, 72, 96, 32, _lib.EUNET_BF16),  # coff + c > ctot
+                (0x1000, 64, 96, -8, _lib.EUNET_BF16),  # coff < 0
+                (0x1000, 64, 96, 32, 2)]:               # neither dtype
+        assert query(*bad) == (-1, -7), bad
+        assert lib.eunet_last_error().decode().startswith(name[len("eunet_"):] + ": ")
+
+
 def test_upsample_index_closed_forms_equal_the_float_rule():
     """The head kernels' integer x2 source indices (common.h up2_src_i) and closed-form adjoint weights
     (up2_adj_w4) restated and checked against up2_src / up2_adj_w's float rule (PyTorch's

@@ -1175,8 +1175,83 @@ def test_pool_up_bwd_unfusable_units(dt):
     torch.cuda.synchronize()
 
 
+def _view_refusals(ops, dt, odd):
+    """The calls of the older launchers with one view that disagrees with the reference view y of shape (1, 2, 2, C),
+    C = two channel units: odd(kind, base shape) builds the disagreeing view ('n': one more sample, 'h' / 'w': one more
+    row / column, 'f32': fp32 storage).  The odd view is always the larger allocation and the launchers take n, h, w
+    and the element type from the reference view, so a call that were accepted would stay inside every buffer."""
+    C = 2 * EOF[dt]
+    z = lambda *s: ops.act(torch.zeros(*s, C, dtype=dt, device=DEV))
+    y, half = z(1, 2, 2), z(1, 1, 1)
+    full, lo = (1, 2, 2), (1, 1, 1)
+    v, part = torch.zeros(C, device=DEV), torch.zeros(64 * C, device=DEV)
+    w, gz = torch.zeros(1, C, device=DEV), torch.zeros(4, 1, device=DEV)
+    calls = {}
+
+    def add(name, kinds, base, fn):
+        for k in kinds:
+            if odd(k, base) is not None:
+                calls[f"{name}-{k}"] = functools.partial(fn, odd(k, base))
+
+    add("bnrelu_pool.pooled", ["f32"], lo, lambda o: ops.bnrelu_pool(y, v, v, None, o))
+    add("bnrelu_pool.act", ["n", "f32"], full, lambda o: ops.bnrelu_pool(y, v, v, o, half))
+    add("bn_bwd_apply.g", ["n"], full, lambda o: ops.bn_bwd_apply(o, y, v, v, v, v, v, v, z(*full)))
+    add("bn_bwd_apply.gy", ["h", "w"], full, lambda o: ops.bn_bwd_apply(z(*full), y, v, v, v, v, v, v, o))
+    for name, run in [("pool_bwd_add", lambda gp, gs, go: ops.pool_bwd_add(y, gp, gs, go)),
+                      ("pool_bwd_add_bnr", lambda gp, gs, go: ops.pool_bwd_add_bnr(y, gp, gs, go, y, v, v, v, v, part))]:
+        add(name + ".gpool", ["n", "f32"], lo, lambda o, run=run: run(o, z(*full), z(*full)))
+        add(name + ".gskip", ["n", "h", "f32"], full, lambda o, run=run: run(half, o, z(*full)))
+        add(name + ".gout", ["n"], full, lambda o, run=run: run(half, z(*full), o))
+    reduce_only = lambda gp, gs: ops.pool_bwd_add_bnr(y, gp, gs, None, y, v, v, v, v, part)
+    add("pool_bwd_add_bnr.reduce.gpool", ["n", "f32"], lo, lambda o: reduce_only(o, z(*full)))
+    add("pool_bwd_add_bnr.reduce.gskip", ["n", "h", "f32"], full, lambda o: reduce_only(half, o))
+    add("conv1x1_bwd.gact", ["n", "h"], full, lambda o: ops.conv1x1_bwd(y, v, v, w, 1, gz, o, part))
+    add("conv1x1_bwd_bnr.gact", ["n", "h"], full, lambda o: ops.conv1x1_bwd_bnr(y, v, v, w, 1, gz, o, part, v, v, part))
+    return calls
+
+
+@dts
+def test_views_must_agree_in_shape(dt):
+    """Every view of a call agrees with the reference view in n, h and w (up to the op's factor 2): one more sample,
+    row or column in any other view is EUNET_ERR_INVALID before anything is launched."""
+    ops = _ops()
+    C = 2 * EOF[dt]
+    grow = {"n": (1, 0, 0), "h": (0, 1, 0), "w": (0, 0, 1)}
+
+    def odd(kind, base):
+        if kind not in grow:
+            return None
+        return ops.act(torch.zeros(*[b + d for b, d in zip(base, grow[kind])], C, dtype=dt, device=DEV))
+
+    calls = _view_refusals(ops, dt, odd)
+    assert len(calls) == 19
+    for name, call in calls.items():
+        with pytest.raises(_err()):
+            call()
+            pytest.fail(f"{name}: accepted")
+    torch.cuda.synchronize()
+
+
+def test_views_must_agree_in_dtype():
+    """The same for the element type: an fp32 view among bf16 ones (the element type is the reference view's, so the
+    fp32 tensor is the larger allocation)."""
+    ops = _ops()
+    C = 2 * EOF[BF16]
+
+    def odd(kind, base):
+        return ops.act(torch.zeros(*base, C, dtype=F32, device=DEV)) if kind == "f32" else None
+
+    calls = _view_refusals(ops, BF16, odd)
+    assert len(calls) == 8
+    for name, call in calls.items():
+        with pytest.raises(_err()):
+            call()
+            pytest.fail(f"{name}: accepted")
+    torch.cuda.synchronize()
+
+
 # ---- D4. upsample adjoints ----------------------------------------------------------------------------------
-UPB_SHAPES = [(1, 1, 1), (2, 1, 5), (2, 5, 1), (1, 8, 2), (1, 9, 7), (2, 17, 3)]
+UPB_SHAPES =[(1, 1, 1), (2, 1, 5), (2, 5, 1), (1, 8, 2), (1, 9, 7), (2, 17, 3)]
 UP_R = 8
 
 

@@ -291,6 +291,20 @@ def test_gate_out_fwd(shape, K):
         assert float(f2[..., C2:].abs().max()) == 0.0, f"pad channels {dt}"
 
 
+def test_gate_out_fwd_rejects_a_larger_f2():
+    """f2 must have the branch outputs' n, h and w: one more sample (the larger allocation: the kernel takes its
+    pixel count from za) is EUNET_ERR_INVALID, for both dtypes."""
+    from eunet._lib import EunetError
+    ops, K = _ops(), 1
+    za = torch.zeros(1, 2, 2, K, device=DEV)
+    b, v = torch.zeros(1, 2, 2, 2 * K, device=DEV), torch.zeros(2 * K, device=DEV)
+    for dt in DTYPES:
+        f2 = torch.zeros(2, 2, 2, 8, dtype=dt, device=DEV)
+        with pytest.raises(EunetError):
+            ops.gate_out_fwd(za, za, K, b, v, v, ops.act(f2, 0, 2 * K))
+    torch.cuda.synchronize()
+
+
 @shapes_and_k
 def test_fusion_out_fwd(shape, K):
     ops, c = _ops(), _case(shape, K)

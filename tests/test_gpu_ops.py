@@ -1048,3 +1048,29 @@ def test_conv3x3_pack_many_matches_pack(dt):
         assert torch.equal(got.view(torch.int16 if dt == torch.bfloat16 else torch.int32),
                            ref.view(torch.int16 if dt == torch.bfloat16 else torch.int32)), (w.shape, flip)
 
+
+def test_unknown_dtype_code_is_refused():
+    """A dtype code that is neither EUNET_F32 nor EUNET_BF16 is EUNET_ERR_INVALID (it used to run the fp32
+    instantiation): the weight packers and the view of eunet_nchw_to_nhwc.  Every buffer is sized for fp32, the
+    widest the kernels could write, and the C ABI is called directly so that nothing rebuilds the arguments."""
+    import ctypes
+    from eunet import _lib
+    ops = _ops()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    w = torch.zeros(8, 8, 3, 3, device=DEV)
+    wp = torch.zeros(ops.conv3x3_packed_bytes(8, 8, torch.float32) // 4, device=DEV)
+    nbytes = ctypes.c_size_t()
+    with pytest.raises(_lib.EunetError):
+        _lib.call("eunet_conv3x3_packed_bytes", 8, 8, 2, ctypes.byref(nbytes))
+    with pytest.raises(_lib.EunetError):
+        _lib.call("eunet_conv3x3_pack", ctypes.c_void_p(w.data_ptr()), 8, 8, 0, ctypes.c_void_p(wp.data_ptr()), 2, stream)
+    descs = (_lib.PackDesc * 1)(_lib.PackDesc(w.data_ptr(), 8, 8, 0, wp.data_ptr()))
+    with pytest.raises(_lib.EunetError):
+        _lib.call("eunet_conv3x3_pack_many", ctypes.cast(descs, ctypes.c_void_p), 1, 2, stream)
+    x, out = torch.zeros(1, 4, 2, 2, device=DEV), torch.zeros(1, 2, 2, 4, device=DEV)
+    view = ops.act(out)
+    view.dtype = 2
+    with pytest.raises(_lib.EunetError):
+        _lib.call("eunet_nchw_to_nhwc", ctypes.c_void_p(x.data_ptr()), ctypes.byref(view), stream)
+    torch.cuda.synchronize()
+
