@@ -19,6 +19,12 @@
 // the target once (16 bytes per lane when H*W is a multiple of 4), reduces in the wave and writes one
 // partial row; a single block sums the partials in fp64 in a fixed order (deterministic).  Backward:
 // analytic per pixel from the saved sums, logits and target read once, the gradient written once.
+//
+// WEIGHTED (eunet_bce_dice_fwd_w / _bwd_w): bce(x,t)_c is multiplied by a per-pixel weight m [N,H,W] (one
+// more stream, read 16 bytes per lane on the vector path); the denominators and the Dice terms are
+// untouched.  The weight enters as a factor of cw_c (forward) and of the BCE coefficient (backward): a
+// multiplication by 1.0f is exact and the rest of the expression is the unweighted one, so m = 1 gives the
+// unweighted bits.  WEIGHTED = false is the code as it was.
 #include "common.h"
 
 EUNET_DEBUG_UNIT(bcedice)
@@ -67,8 +73,8 @@ __device__ __forceinline__ float target_of(int64_t traw, int c, const eunet_bce_
 }
 
 // acc: [0] bce sum, [1+c] I, [1+K+c] S, [1+2K+c] T, [1+3K] valid pixels, [2+3K] out-of-range targets
-template <int K>
-__device__ __forceinline__ void fwd_px(const float (&x)[K], int64_t traw, const eunet_bce_dice_params& prm,
+template <int K, bool WEIGHTED>
+__device__ __forceinline__ void fwd_px(const float (&x)[K], int64_t traw, float wt, const eunet_bce_dice_params& prm,
                                        float (&acc)[3 + 3 * K]) {
   const int cls = classify(traw, K, prm);
   if (cls == 2) acc[2 + 3 * K] += 1.f;
@@ -78,21 +84,23 @@ __device__ __forceinline__ void fwd_px(const float (&x)[K], int64_t traw, const 
   for (int c = 0; c < K; ++c) {
     const Sig s = sigmoid_terms<true>(x[c]);
     const float t = target_of(traw, c, prm);
-    acc[0] += prm.class_weight[c] * (prm.pos_weight[c] * t * s.spn + (1.f - t) * s.spp);
+    const float cw = WEIGHTED ? wt * prm.class_weight[c] : prm.class_weight[c];
+    acc[0] += cw * (prm.pos_weight[c] * t * s.spn + (1.f - t) * s.spp);
     acc[1 + c] += s.p * t;
     acc[1 + K + c] += s.p;
     acc[1 + 2 * K + c] += t;
   }
 }
 
-template <int K, bool VEC>
-__global__ __launch_bounds__(NT) void bce_dice_fwd_kernel(const float* logits, const int64_t* target, int HW,
-                                                          eunet_bce_dice_params prm, float* part) {
+template <int K, bool VEC, bool WEIGHTED>
+__global__ __launch_bounds__(NT) void bce_dice_fwd_kernel(const float* logits, const int64_t* target, const float* pw,
+                                                          int HW, eunet_bce_dice_params prm, float* part) {
   constexpr int NV = 3 + 3 * K;
   __shared__ float red[4][NV];
   const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const float* lg = logits + (long long)n * K * HW;
   const int64_t* tg = target + (long long)n * HW;
+  const float* wg = WEIGHTED ? pw + (long long)n * HW : nullptr;
   float acc[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) acc[i] = 0.f;
@@ -108,12 +116,14 @@ __global__ __launch_bounds__(NT) void bce_dice_fwd_kernel(const float* logits, c
       const i64x2 t01 = *reinterpret_cast<const i64x2*>(tg + p);
       const i64x2 t23 = *reinterpret_cast<const i64x2*>(tg + p + 2);
       const int64_t tr[4] = {t01[0], t01[1], t23[0], t23[1]};
+      f32x4 wv = {1.f, 1.f, 1.f, 1.f};
+      if (WEIGHTED) wv = *reinterpret_cast<const f32x4*>(wg + p);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float x[K];
 #pragma unroll
         for (int c = 0; c < K; ++c) x[c] = xv[c][j];
-        fwd_px<K>(x, tr[j], prm, acc);
+        fwd_px<K, WEIGHTED>(x, tr[j], wv[j], prm, acc);
       }
     }
   } else {
@@ -122,7 +132,7 @@ __global__ __launch_bounds__(NT) void bce_dice_fwd_kernel(const float* logits, c
       float x[K];
 #pragma unroll
       for (int c = 0; c < K; ++c) x[c] = lg[(long long)c * HW + p];
-      fwd_px<K>(x, tg[p], prm, acc);
+      fwd_px<K, WEIGHTED>(x, tg[p], WEIGHTED ? wg[p] : 1.f, prm, acc);
     }
   }
 #pragma unroll
@@ -237,9 +247,10 @@ __device__ __forceinline__ void bwd_px(const float (&x)[K], int64_t traw, const 
 }
 
 // VEC: one thread per group of 4 pixels (HW % 4 == 0, so a group never straddles two samples)
-template <int K, bool VEC>
-__global__ __launch_bounds__(NT) void bce_dice_bwd_kernel(const float* logits, const int64_t* target, int N, int HW,
-                                                          eunet_bce_dice_params prm, const float* sums,
+// WEIGHTED: bwd_px gets cb * m(x) for cb
+template <int K, bool VEC, bool WEIGHTED>
+__global__ __launch_bounds__(NT) void bce_dice_bwd_kernel(const float* logits, const int64_t* target, const float* pw,
+                                                          int N, int HW, eunet_bce_dice_params prm, const float* sums,
                                                           const float* gloss, float* glog) {
   constexpr int NV = 3 + 3 * K;
   constexpr int PER = VEC ? 4 : 1;
@@ -263,12 +274,14 @@ __global__ __launch_bounds__(NT) void bce_dice_bwd_kernel(const float* logits, c
     const i64x2 t01 = *reinterpret_cast<const i64x2*>(target + id);
     const i64x2 t23 = *reinterpret_cast<const i64x2*>(target + id + 2);
     const int64_t tr[4] = {t01[0], t01[1], t23[0], t23[1]};
+    f32x4 wv = {1.f, 1.f, 1.f, 1.f};
+    if (WEIGHTED) wv = *reinterpret_cast<const f32x4*>(pw + id);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float x[K], g[K];
 #pragma unroll
       for (int c = 0; c < K; ++c) x[c] = xv[c][j];
-      bwd_px<K>(x, tr[j], prm, dc, cb, g0, g);
+      bwd_px<K>(x, tr[j], prm, dc, WEIGHTED ? cb * wv[j] : cb, g0, g);
 #pragma unroll
       for (int c = 0; c < K; ++c) gv[c][j] = g[c];
     }
@@ -278,7 +291,7 @@ __global__ __launch_bounds__(NT) void bce_dice_bwd_kernel(const float* logits, c
     float x[K], g[K];
 #pragma unroll
     for (int c = 0; c < K; ++c) x[c] = lg[(long long)c * HW];
-    bwd_px<K>(x, target[id], prm, dc, cb, g0, g);
+    bwd_px<K>(x, target[id], prm, dc, WEIGHTED ? cb * pw[id] : cb, g0, g);
 #pragma unroll
     for (int c = 0; c < K; ++c) gl[(long long)c * HW] = g[c];
   }
@@ -343,6 +356,61 @@ bool resolve(const eunet_bce_dice_params* params, int k, eunet_bce_dice_params* 
   return true;
 }
 
+// one launcher per direction for the unweighted and the weighted entry points (pw == nullptr: unweighted)
+int bce_dice_fwd_launch(const float* logits, const int64_t* target, const float* pw, int n, int k, int h, int w,
+                        const eunet_bce_dice_params* params, float* sums, float* loss, float* parts, void* ws,
+                        void* stream, const char* what) {
+  EUNET_REQUIRE(logits && target && sums && loss && ws && n > 0 && n <= 64 && k >= 1 && k <= 3 && h > 0 && w > 0 &&
+                    (long long)h * w < (1ll << 31) - LPIX,
+                "%s: bad args (N <= 64, K <= 3)", what);
+  eunet_bce_dice_params prm;
+  if (!resolve(params, k, &prm, what)) return EUNET_ERR_INVALID;
+  const int HW = h * w, tiles = cdiv(HW, LPIX);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(tiles, n);
+  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)target % 16 == 0) &&
+                   ((uintptr_t)pw % 16 == 0);
+#define BK(KK, VV)                                                                                        \
+  if (pw)                                                                                                 \
+    bce_dice_fwd_kernel<KK, VV, true><<<grid, NT, 0, s>>>(logits, target, pw, HW, prm, (float*)ws);       \
+  else                                                                                                    \
+    bce_dice_fwd_kernel<KK, VV, false><<<grid, NT, 0, s>>>(logits, target, nullptr, HW, prm, (float*)ws);
+#define BF(KK)                                                                                            \
+  if (vec) { BK(KK, true) } else { BK(KK, false) }                                                        \
+  bce_dice_finalize_kernel<KK><<<1, 256, 0, s>>>((const float*)ws, tiles, n, prm, sums, loss, parts);
+  if (k == 1) { BF(1) } else if (k == 2) { BF(2) } else { BF(3) }
+#undef BF
+#undef BK
+  return eunet::check_launch(what);
+}
+
+int bce_dice_bwd_launch(const float* logits, const int64_t* target, const float* pw, int n, int k, int h, int w,
+                        const eunet_bce_dice_params* params, const float* sums, const float* gloss, float* glogits,
+                        void* stream, const char* what) {
+  EUNET_REQUIRE(logits && target && sums && gloss && glogits && n > 0 && n <= 64 && k >= 1 && k <= 3 && h > 0 &&
+                    w > 0 && (long long)h * w < (1ll << 31) - LPIX,
+                "%s: bad args (N <= 64, K <= 3)", what);
+  eunet_bce_dice_params prm;
+  if (!resolve(params, k, &prm, what)) return EUNET_ERR_INVALID;
+  const int HW = h * w;
+  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)target % 16 == 0) &&
+                   ((uintptr_t)glogits % 16 == 0) && ((uintptr_t)pw % 16 == 0);
+  const long long threads = (long long)n * HW / (vec ? 4 : 1);
+  const unsigned g = (unsigned)((threads + NT - 1) / NT);
+  hipStream_t s = (hipStream_t)stream;
+#define BK(KK, VV)                                                                                               \
+  if (pw)                                                                                                        \
+    bce_dice_bwd_kernel<KK, VV, true><<<g, NT, 0, s>>>(logits, target, pw, n, HW, prm, sums, gloss, glogits);    \
+  else                                                                                                           \
+    bce_dice_bwd_kernel<KK, VV, false><<<g, NT, 0, s>>>(logits, target, nullptr, n, HW, prm, sums, gloss, glogits);
+#define BB(KK) \
+  if (vec) { BK(KK, true) } else { BK(KK, false) }
+  if (k == 1) { BB(1) } else if (k == 2) { BB(2) } else { BB(3) }
+#undef BB
+#undef BK
+  return eunet::check_launch(what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,50 +437,31 @@ int eunet_bce_dice_workspace_bytes(int n, int k, int h, int w, size_t* bytes) {
 int eunet_bce_dice_fwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
                        const eunet_bce_dice_params* params, float* sums, float* loss, float* parts, void* ws,
                        void* stream) {
-  EUNET_REQUIRE(logits && target && sums && loss && ws && n > 0 && n <= 64 && k >= 1 && k <= 3 && h > 0 && w > 0 &&
-                    (long long)h * w < (1ll << 31) - LPIX,
-                "bce_dice_fwd: bad args (N <= 64, K <= 3)");
-  eunet_bce_dice_params prm;
-  if (!resolve(params, k, &prm, "bce_dice_fwd")) return EUNET_ERR_INVALID;
-  const int HW = h * w, tiles = cdiv(HW, LPIX);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(tiles, n);
-  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)target % 16 == 0);
-#define BF(KK)                                                                                                  \
-  if (vec)                                                                                                      \
-    bce_dice_fwd_kernel<KK, true><<<grid, NT, 0, s>>>(logits, target, HW, prm, (float*)ws);                     \
-  else                                                                                                          \
-    bce_dice_fwd_kernel<KK, false><<<grid, NT, 0, s>>>(logits, target, HW, prm, (float*)ws);                    \
-  bce_dice_finalize_kernel<KK><<<1, 256, 0, s>>>((const float*)ws, tiles, n, prm, sums, loss, parts);
-  if (k == 1) { BF(1) } else if (k == 2) { BF(2) } else { BF(3) }
-#undef BF
-  EUNET_LAUNCH_CHECK("bce_dice_fwd");
-  return EUNET_OK;
+  return bce_dice_fwd_launch(logits, target, nullptr, n, k, h, w, params, sums, loss, parts, ws, stream,
+                             "bce_dice_fwd");
+}
+
+int eunet_bce_dice_fwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k, int h,
+                         int w, const eunet_bce_dice_params* params, float* sums, float* loss, float* parts, void* ws,
+                         void* stream) {
+  EUNET_REQUIRE(pixel_weight, "bce_dice_fwd_w: pixel_weight must not be null");
+  return bce_dice_fwd_launch(logits, target, pixel_weight, n, k, h, w, params, sums, loss, parts, ws, stream,
+                             "bce_dice_fwd_w");
 }
 
 int eunet_bce_dice_bwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
                        const eunet_bce_dice_params* params, const float* sums, const float* gloss, float* glogits,
                        void* stream) {
-  EUNET_REQUIRE(logits && target && sums && gloss && glogits && n > 0 && n <= 64 && k >= 1 && k <= 3 && h > 0 &&
-                    w > 0 && (long long)h * w < (1ll << 31) - LPIX,
-                "bce_dice_bwd: bad args (N <= 64, K <= 3)");
-  eunet_bce_dice_params prm;
-  if (!resolve(params, k, &prm, "bce_dice_bwd")) return EUNET_ERR_INVALID;
-  const int HW = h * w;
-  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)target % 16 == 0) &&
-                   ((uintptr_t)glogits % 16 == 0);
-  const long long threads = (long long)n * HW / (vec ? 4 : 1);
-  const unsigned g = (unsigned)((threads + NT - 1) / NT);
-  hipStream_t s = (hipStream_t)stream;
-#define BB(KK)                                                                                        \
-  if (vec)                                                                                            \
-    bce_dice_bwd_kernel<KK, true><<<g, NT, 0, s>>>(logits, target, n, HW, prm, sums, gloss, glogits); \
-  else                                                                                                \
-    bce_dice_bwd_kernel<KK, false><<<g, NT, 0, s>>>(logits, target, n, HW, prm, sums, gloss, glogits);
-  if (k == 1) { BB(1) } else if (k == 2) { BB(2) } else { BB(3) }
-#undef BB
-  EUNET_LAUNCH_CHECK("bce_dice_bwd");
-  return EUNET_OK;
+  return bce_dice_bwd_launch(logits, target, nullptr, n, k, h, w, params, sums, gloss, glogits, stream,
+                             "bce_dice_bwd");
+}
+
+int eunet_bce_dice_bwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k, int h,
+                         int w, const eunet_bce_dice_params* params, const float* sums, const float* gloss,
+                         float* glogits, void* stream) {
+  EUNET_REQUIRE(pixel_weight, "bce_dice_bwd_w: pixel_weight must not be null");
+  return bce_dice_bwd_launch(logits, target, pixel_weight, n, k, h, w, params, sums, gloss, glogits, stream,
+                             "bce_dice_bwd_w");
 }
 
 int eunet_sigmoid_crop(const float* logits, int k, int hp, int wp, int h, int w, int flip_h, int flip_w,

@@ -19,6 +19,12 @@
 // (F.cross_entropy raises / device-asserts): they are counted into sums[N*NV + 1] for the
 // host to report at its next synchronisation, and contribute nothing here.
 // Backward is analytic per pixel from the saved per-(sample,class) sums.
+//
+// WEIGHTED (eunet_loss_fwd_w / eunet_loss_bwd_w): the per-pixel focal summand is multiplied by a
+// per-pixel weight m [N,H,W] (the U-Net border weight map of weightmap.hip), F_den stays N*H*W, Dice
+// and Tversky are untouched.  The weight enters as a factor of alpha_t (forward) and of the finished
+// focal coefficient (backward): a multiplication by 1.0f is exact and the rest of the expression is
+// the unweighted one, so m = 1 gives the unweighted bits.  WEIGHTED = false is the code as it was.
 #include "common.h"
 
 namespace {
@@ -72,9 +78,9 @@ __device__ __forceinline__ void focal_pow(float om, float gamma, float& pg, floa
   pg1 = powf(om, gamma - 1.f);
 }
 
-template <int K>
-__global__ __launch_bounds__(NT) void loss_fwd_kernel(const float* logits, const int64_t* target, int HW,
-                                                      eunet_loss_params prm, float* part) {
+template <int K, bool WEIGHTED>
+__global__ __launch_bounds__(NT) void loss_fwd_kernel(const float* logits, const int64_t* target, const float* pw,
+                                                      int HW, eunet_loss_params prm, float* part) {
   constexpr int NV = 3 + 3 * K;  // focal sum, I/S/T per class, ce-weight sum, bad-target count
   __shared__ float red[4][NV];
   const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -99,7 +105,8 @@ __global__ __launch_bounds__(NT) void loss_fwd_kernel(const float* logits, const
       const float pt = expf(-ce);
       float pg, pg1;
       focal_pow(1.f - pt, prm.gamma, pg, pg1);
-      acc[0] += prm.alpha[t] * pg * ce;
+      const float al = WEIGHTED ? pw[(long long)n * HW + p] * prm.alpha[t] : prm.alpha[t];
+      acc[0] += al * pg * ce;
       acc[1 + 3 * K] += prm.ce_weight[t];
     } else if (!ign) {
       acc[2 + 3 * K] += 1.f;
@@ -193,9 +200,9 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* part, i
   }
 }
 
-template <int K>
-__global__ void loss_bwd_kernel(const float* logits, const int64_t* target, int N, int HW, eunet_loss_params prm,
-                                const float* sums, const float* gloss, float* glog) {
+template <int K, bool WEIGHTED>
+__global__ void loss_bwd_kernel(const float* logits, const int64_t* target, const float* pw, int N, int HW,
+                                eunet_loss_params prm, const float* sums, const float* gloss, float* glog) {
   constexpr int NV = 3 + 3 * K;
   const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= (long long)N * HW) return;
@@ -217,6 +224,7 @@ __global__ void loss_bwd_kernel(const float* logits, const int64_t* target, int 
     focal_pow(1.f - pt, prm.gamma, pg, pg1);
     const float dfdce = prm.alpha[t] * (pg + ce * prm.gamma * pg1 * pt);
     fcoef = prm.w_focal * dfdce * prm.ce_weight[t] / sums[N * NV];
+    if (WEIGHTED) fcoef *= pw[id];
   }
   const float invn = 1.f / (float)N;
   const float* sm = sums + n * NV;
@@ -266,37 +274,84 @@ int eunet_loss_workspace_bytes(int n, int k, int h, int w, size_t* bytes) {
   return EUNET_OK;
 }
 
-int eunet_loss_fwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
-                   const eunet_loss_params* params, float* sums, float* loss, float* parts, void* ws, void* stream) {
-  EUNET_REQUIRE(logits && target && sums && loss && ws && n > 0 && n <= 64 && k >= 1 && k <= 3,
-                "loss_fwd: bad args (N <= 64, K <= 3)");
+}  // extern "C"
+
+// one launcher per direction for the unweighted and the weighted entry points (pw == nullptr: unweighted)
+namespace {
+int loss_fwd_launch(const float* logits, const int64_t* target, const float* pw, int n, int k, int h, int w,
+                    const eunet_loss_params* params, float* sums, float* loss, float* parts, void* ws, void* stream,
+                    const char* what) {
   const eunet_loss_params prm = params ? *params : kReferenceParams;
-  EUNET_REQUIRE(prm.class_div > 0.f, "loss_fwd: class_div must be > 0");
+  EUNET_REQUIRE(prm.class_div > 0.f, "%s: class_div must be > 0", what);
+  EUNET_REQUIRE(!pw || prm.focal_norm == 0,
+                "%s: focal_norm = 1 with a pixel weight is not defined (its denominator would need a definition)", what);
   const int HW = h * w, tiles = cdiv(HW, LPIX);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(tiles, n);
 #define LF(KK)                                                                                        \
-  loss_fwd_kernel<KK><<<grid, NT, 0, s>>>(logits, target, HW, prm, (float*)ws);                       \
+  if (pw)                                                                                             \
+    loss_fwd_kernel<KK, true><<<grid, NT, 0, s>>>(logits, target, pw, HW, prm, (float*)ws);           \
+  else                                                                                                \
+    loss_fwd_kernel<KK, false><<<grid, NT, 0, s>>>(logits, target, nullptr, HW, prm, (float*)ws);     \
   loss_finalize_kernel<KK><<<1, 256, 0, s>>>((const float*)ws, tiles, n, HW, prm, sums, loss, parts);
   if (k == 1) { LF(1) } else if (k == 2) { LF(2) } else { LF(3) }
 #undef LF
-  EUNET_LAUNCH_CHECK("loss_fwd");
-  return EUNET_OK;
+  return eunet::check_launch(what);
+}
+
+int loss_bwd_launch(const float* logits, const int64_t* target, const float* pw, int n, int k, int h, int w,
+                    const eunet_loss_params* params, const float* sums, const float* gloss, float* glogits,
+                    void* stream, const char* what) {
+  const eunet_loss_params prm = params ? *params : kReferenceParams;
+  EUNET_REQUIRE(!pw || prm.focal_norm == 0, "%s: focal_norm = 1 with a pixel weight is not defined", what);
+  const long long total = (long long)n * h * w;
+  const unsigned g = (unsigned)((total + 255) / 256);
+  hipStream_t s = (hipStream_t)stream;
+#define LB(KK)                                                                                             \
+  if (pw)                                                                                                  \
+    loss_bwd_kernel<KK, true><<<g, 256, 0, s>>>(logits, target, pw, n, h * w, prm, sums, gloss, glogits);  \
+  else                                                                                                     \
+    loss_bwd_kernel<KK, false><<<g, 256, 0, s>>>(logits, target, nullptr, n, h * w, prm, sums, gloss, glogits);
+  if (k == 1) { LB(1) } else if (k == 2) { LB(2) } else { LB(3) }
+#undef LB
+  return eunet::check_launch(what);
+}
+}  // namespace
+
+extern "C" {
+
+int eunet_loss_fwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
+                   const eunet_loss_params* params, float* sums, float* loss, float* parts, void* ws, void* stream) {
+  EUNET_REQUIRE(logits && target && sums && loss && ws && n > 0 && n <= 64 && k >= 1 && k <= 3,
+                "loss_fwd: bad args (N <= 64, K <= 3)");
+  return loss_fwd_launch(logits, target, nullptr, n, k, h, w, params, sums, loss, parts, ws, stream, "loss_fwd");
+}
+
+int eunet_loss_fwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k, int h, int w,
+                     const eunet_loss_params* params, float* sums, float* loss, float* parts, void* ws,
+                     void* stream) {
+  EUNET_REQUIRE(logits && target && pixel_weight && sums && loss && ws && n > 0 && n <= 64 && k >= 1 && k <= 3 &&
+                    h > 0 && w > 0,
+                "loss_fwd_w: bad args (N <= 64, K <= 3, pixel_weight non-null)");
+  return loss_fwd_launch(logits, target, pixel_weight, n, k, h, w, params, sums, loss, parts, ws, stream,
+                         "loss_fwd_w");
 }
 
 int eunet_loss_bwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
                    const eunet_loss_params* params, const float* sums, const float* gloss, float* glogits,
                    void* stream) {
   EUNET_REQUIRE(logits && target && sums && gloss && glogits && n > 0 && k >= 1 && k <= 3, "loss_bwd: bad args");
-  const eunet_loss_params prm = params ? *params : kReferenceParams;
-  const long long total = (long long)n * h * w;
-  const unsigned g = (unsigned)((total + 255) / 256);
-  hipStream_t s = (hipStream_t)stream;
-  if (k == 1) loss_bwd_kernel<1><<<g, 256, 0, s>>>(logits, target, n, h * w, prm, sums, gloss, glogits);
-  else if (k == 2) loss_bwd_kernel<2><<<g, 256, 0, s>>>(logits, target, n, h * w, prm, sums, gloss, glogits);
-  else loss_bwd_kernel<3><<<g, 256, 0, s>>>(logits, target, n, h * w, prm, sums, gloss, glogits);
-  EUNET_LAUNCH_CHECK("loss_bwd");
-  return EUNET_OK;
+  return loss_bwd_launch(logits, target, nullptr, n, k, h, w, params, sums, gloss, glogits, stream, "loss_bwd");
+}
+
+int eunet_loss_bwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k, int h, int w,
+                     const eunet_loss_params* params, const float* sums, const float* gloss, float* glogits,
+                     void* stream) {
+  EUNET_REQUIRE(logits && target && pixel_weight && sums && gloss && glogits && n > 0 && k >= 1 && k <= 3 && h > 0 &&
+                    w > 0,
+                "loss_bwd_w: bad args (pixel_weight non-null)");
+  return loss_bwd_launch(logits, target, pixel_weight, n, k, h, w, params, sums, gloss, glogits, stream,
+                         "loss_bwd_w");
 }
 
 }  // extern "C"

@@ -46,6 +46,8 @@ class BCEDiceParams(ctypes.Structure):
 
 
 BCE_TARGET_AUTO, BCE_TARGET_ONEHOT, BCE_TARGET_FOREGROUND = 0, 1, 2  # EUNET_BCE_TARGET_*
+WMAP_RADIUS_AUTO = -1  # EUNET_WMAP_RADIUS_AUTO
+WMAP_MAX_RADIUS = 48
 
 
 class OptTensor(ctypes.Structure):
@@ -107,6 +109,12 @@ SIGNATURES = {
     "eunet_bce_dice_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],
     "eunet_bce_dice_fwd": [_f, _f, c_int, c_int, c_int, c_int, POINTER(BCEDiceParams), _f, _f, _f, _f, c_void_p],
     "eunet_bce_dice_bwd": [_f, _f, c_int, c_int, c_int, c_int, POINTER(BCEDiceParams), _f, _f, _f, c_void_p],
+    "eunet_border_weight_map": [_f, _f, c_int, c_int, c_int, POINTER(c_float * 3), c_float, c_float, c_int, _f, c_void_p],
+    "eunet_separate_instances": [_f, _f, c_int, c_int, c_int, _f, _f, c_void_p],
+    "eunet_loss_fwd_w": [_f, _f, _f, c_int, c_int, c_int, c_int, POINTER(LossParams), _f, _f, _f, _f, c_void_p],
+    "eunet_loss_bwd_w": [_f, _f, _f, c_int, c_int, c_int, c_int, POINTER(LossParams), _f, _f, _f, c_void_p],
+    "eunet_bce_dice_fwd_w": [_f, _f, _f, c_int, c_int, c_int, c_int, POINTER(BCEDiceParams), _f, _f, _f, _f, c_void_p],
+    "eunet_bce_dice_bwd_w": [_f, _f, _f, c_int, c_int, c_int, c_int, POINTER(BCEDiceParams), _f, _f, _f, c_void_p],
     "eunet_bn_bwd_tiles": [_P, POINTER(c_int)],
     "eunet_bn_bwd_reduce": [_P, _P, _f, _f, _f, _f, _f, c_void_p],
     "eunet_colsum_ws_bytes": [c_int, c_int, POINTER(c_size_t)],

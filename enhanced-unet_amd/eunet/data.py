@@ -31,6 +31,10 @@ seeded by one np.random draw -- sync-free and faster, same Python `random` decis
 noise values and a shifted np.random stream.  DataLoader(workers=W, prefetch=P) decodes JPEG + JSON in W threads and runs the device
 part of the next P batches on a side stream while the trainer consumes the current one; the
 Python `random` draws stay in item order (one producer thread).
+
+CellDataset(..., weight_map={...}) (not in the reference): every item also carries the U-Net border
+weight map of its polygons (ops.border_weight_map, include/eunet.h) and the instance label map it was
+computed from; it draws no random number, so the augmentation stream is the one of weight_map=None.
 """
 from __future__ import annotations
 
@@ -103,7 +107,7 @@ def _host_load_args(args):
 class CellDataset:
     def __init__(self, data_dir: str, split: str = "train", transform=None, max_size: int = 1024,
                  device: str = "cuda", cell_preprocess: bool = True, host_noise: bool = True,
-                 host_ratio: bool = False):
+                 host_ratio: bool = False, weight_map=None):
         self.data_dir, self.split, self.transform, self.max_size = data_dir, split, transform, max_size
         self.device = device
         self.cell_preprocess = cell_preprocess  # dataset.py:204 (always on in the reference)
@@ -115,6 +119,8 @@ class CellDataset:
         # host_ratio: read the live ratio back to the host (round 2's path; one sync per sample)
         self.host_ratio = host_ratio
         self._noise_gen = None
+        # weight_map: None (every item exactly as without the feature) or a dict of WEIGHT_MAP_DEFAULTS' keys
+        self.weight_map = self._weight_map_config(weight_map)
         all_files = sorted(f for f in os.listdir(data_dir) if f.endswith(".jpg"))
         n_total = len(all_files)
         n_train, n_val = int(n_total * 0.7), int(n_total * 0.15)
@@ -127,6 +133,45 @@ class CellDataset:
 
     def __len__(self):
         return len(self.files)
+
+    WEIGHT_MAP_DEFAULTS = dict(w0=10.0, sigma=5.0, class_weight=(1.0, 1.0, 1.0), radius=None, separate=False)
+
+    @classmethod
+    def _weight_map_config(cls, cfg):
+        """The weight_map argument checked on the host (the kernel's own rules, raised as ValueError here)."""
+        if cfg is None:
+            return None
+        if not isinstance(cfg, dict):
+            raise ValueError(f"weight_map must be None or a dict, got {type(cfg).__name__}")
+        unknown = set(cfg) - set(cls.WEIGHT_MAP_DEFAULTS)
+        if unknown:
+            raise ValueError(f"weight_map: unknown key(s) {sorted(unknown)}; known: {sorted(cls.WEIGHT_MAP_DEFAULTS)}")
+        c = dict(cls.WEIGHT_MAP_DEFAULTS, **cfg)
+        c["w0"], c["sigma"] = float(c["w0"]), float(c["sigma"])
+        c["class_weight"] = tuple(float(v) for v in c["class_weight"])
+        if not c["sigma"] > 0.0 or not c["w0"] >= 0.0 or len(c["class_weight"]) != 3:
+            raise ValueError(f"weight_map: needs sigma > 0, w0 >= 0 and 3 class weights, got {cfg}")
+        r = int(np.ceil(5.5 * c["sigma"])) if c["radius"] is None else int(c["radius"])
+        if not 1 <= r <= 48:
+            raise ValueError(f"weight_map: radius {r} outside 1..48 (the default is ceil(5.5 sigma))")
+        c["radius"], c["separate"] = r, bool(c["separate"])
+        return c
+
+    def _weight_map_item(self, polys, h, w, flips, mask, device):
+        """(semantic mask, weight map, instance label map) of one item: polygon i filled with id i + 1 by the
+        semantic mask's own rasteriser (later polygons overwrite earlier ones, as there), mirrored by the flips
+        _augment took; enqueued on the current stream, no random draw, no host synchronisation."""
+        c = self.weight_map
+        inst = ops.rasterize_polygons(polys, list(range(1, len(polys) + 1)), h, w, device)
+        if flips[0]:
+            inst = ops.flip_mask(inst, 1)
+        if flips[1]:
+            inst = ops.flip_mask(inst, 0)
+        if c["separate"]:
+            inst, mask = ops.separate_instances(inst, mask)
+        wmap = ops.border_weight_map(inst, mask, class_weight=c["class_weight"], w0=c["w0"], sigma=c["sigma"],
+                                     radius=c["radius"])
+        return mask, wmap, inst
 
     @staticmethod
     def _apply_cell_specific_preprocessing(img, polys, labels):
@@ -229,8 +274,12 @@ class CellDataset:
         instance_masks = list(ops.rasterize_instances(polys, h, w, img.device, flip_h=flips[0], flip_v=flips[1]))
         tensor = self.transform(img) if self.transform else ops.to_tensor(img)
         # dataset.py:313-321; bboxes stay in the unflipped frame, as the reference leaves them
-        return {"image": tensor, "instance_masks": instance_masks, "instance_labels": labels, "bboxes": bboxes,
+        item = {"image": tensor, "instance_masks": instance_masks, "instance_labels": labels, "bboxes": bboxes,
                 "semantic_mask": mask, "image_id": name, "original_size": original_size}
+        if self.weight_map is not None:
+            item["semantic_mask"], item["weight_map"], item["instance_label_map"] = self._weight_map_item(
+                polys, h, w, flips, mask, img.device)
+        return item
 
 
 def collate_fn(batch):

@@ -169,6 +169,55 @@ class CombinedLossFunction(torch.autograd.Function):
         return glog, None, None, None
 
 
+def _check_pixel_weight(pixel_weight, logits, target, what: str):
+    """The rules of a per-pixel weight: float32, contiguous, on the logits' device, of the target's shape, and
+    no gradient (the weight takes none)."""
+    if not isinstance(pixel_weight, torch.Tensor):
+        raise ValueError(f"{what}: pixel_weight must be a tensor, got {type(pixel_weight).__name__}")
+    if pixel_weight.requires_grad:
+        raise ValueError(f"{what}: pixel_weight takes no gradient (requires_grad is set)")
+    if pixel_weight.dtype != torch.float32:
+        raise ValueError(f"{what}: pixel_weight must be float32, got {pixel_weight.dtype}")
+    if pixel_weight.shape != target.shape:
+        raise ValueError(f"{what}: pixel_weight {tuple(pixel_weight.shape)} does not match target "
+                         f"{tuple(target.shape)}")
+    if pixel_weight.device != logits.device:
+        raise ValueError(f"{what}: pixel_weight is on {pixel_weight.device}, the logits on {logits.device}")
+    if not pixel_weight.is_contiguous():
+        raise ValueError(f"{what}: pixel_weight must be contiguous")
+
+
+class WeightedCombinedLossFunction(torch.autograd.Function):
+    """CombinedLossFunction with the focal summand multiplied by a per-pixel weight (eunet_loss_fwd_w)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, pixel_weight, params, track_targets):
+        logits = logits.contiguous().float()
+        target = target.contiguous().long()
+        n, k, h, w = logits.shape
+        if target.shape != (n, h, w):
+            raise ValueError(f"target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+        dev = logits.device
+        sums = torch.empty(ops.loss_sums_len(n, k), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        ws = torch.empty(ops.loss_workspace_bytes(n, k, h, w), dtype=torch.uint8, device=dev)
+        ops.loss_fwd_w(logits, target, pixel_weight, params, sums, loss, parts, ws)
+        if track_targets:
+            _record_bad(sums)
+        ctx.save_for_backward(logits, target, pixel_weight, sums)
+        ctx.params = params
+        ctx.mark_non_differentiable(parts)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, gloss, gparts):
+        logits, target, pixel_weight, sums = ctx.saved_tensors
+        glog = torch.empty_like(logits)
+        ops.loss_bwd_w(logits, target, pixel_weight, ctx.params, sums, gloss.contiguous().float().reshape(1), glog)
+        return glog, None, None, None, None
+
+
 class ConsistencyFunction(torch.autograd.Function):
     """sum_b c_b (1/B) sum_i MSE(softmax(branch_b[i]), softmax(fused[i])) (train_eval.py:207-232;
     the fused probabilities are not detached in the reference, so both sides get gradients)."""
@@ -197,11 +246,22 @@ def consistency_loss(fused, br0, br1, c0: float, c1: float):
 
 
 def combined_loss(logits: torch.Tensor, target: torch.Tensor, return_parts: bool = False,
-                  params: Optional[LossParams] = None, validate: bool = False, track_targets: bool = True):
+                  params: Optional[LossParams] = None, validate: bool = False, track_targets: bool = True,
+                  pixel_weight: Optional[torch.Tensor] = None):
     """Batched train_eval loss: logits [B,K,H,W] (already at mask size), target [B,H,W]
     -> (1/B) sum_b [w_focal focal_b + w_dice dice_b + w_tversky tversky_b] (params: None =
-    the reference Trainer's 2.5 / 2.5 / 1.0 configuration)."""
-    loss, parts = CombinedLossFunction.apply(logits, target, params, track_targets)
+    the reference Trainer's 2.5 / 2.5 / 1.0 configuration).  pixel_weight (float32 [B,H,W], e.g.
+    ops.border_weight_map): multiplies the per-pixel focal summand, the pixel mean keeps its N*H*W
+    denominator, Dice and Tversky are untouched; it takes no gradient and cannot be combined with
+    focal_norm = 1."""
+    if pixel_weight is None:
+        loss, parts = CombinedLossFunction.apply(logits, target, params, track_targets)
+    else:
+        _check_pixel_weight(pixel_weight, logits, target, "combined_loss")
+        if params is not None and params.focal_norm != 0:
+            raise ValueError("combined_loss: focal_norm = 1 with a pixel_weight is not defined (its denominator "
+                             "would need a definition of its own)")
+        loss, parts = WeightedCombinedLossFunction.apply(logits, target, pixel_weight, params, track_targets)
     if validate:
         check_targets()
     return (loss, parts) if return_parts else loss
@@ -277,13 +337,55 @@ class BCEDiceFunction(torch.autograd.Function):
         return glog, None, None, None
 
 
+class WeightedBCEDiceFunction(torch.autograd.Function):
+    """BCEDiceFunction with bce(x,t)_c multiplied by a per-pixel weight (eunet_bce_dice_fwd_w)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, pixel_weight, params, track_targets):
+        logits = logits.contiguous().float()
+        target = target.contiguous().long()
+        n, k, h, w = logits.shape
+        check_bce_dice_mode(params, k)
+        if not logits.is_cuda or not target.is_cuda:
+            raise _lib.EunetError("bce_dice_loss needs device tensors (no CPU fallback)")
+        dev = logits.device
+        sums = torch.empty(ops.bce_dice_sums_len(n, k), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        ws = torch.empty(ops.bce_dice_workspace_bytes(n, k, h, w), dtype=torch.uint8, device=dev)
+        ops.bce_dice_fwd_w(logits, target, pixel_weight, params, sums, loss, parts, ws)
+        if track_targets:
+            _record_bad(sums)
+        ctx.save_for_backward(logits, target, pixel_weight, sums)
+        ctx.params = params
+        ctx.mark_non_differentiable(parts)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, gloss, gparts):
+        logits, target, pixel_weight, sums = ctx.saved_tensors
+        glog = torch.empty_like(logits)
+        ops.bce_dice_bwd_w(logits, target, pixel_weight, ctx.params, sums, gloss.contiguous().float().reshape(1), glog)
+        return glog, None, None, None, None
+
+
 def bce_dice_loss(logits: torch.Tensor, target: torch.Tensor, return_parts: bool = False,
-                  params: Optional[BCEDiceParams] = None, validate: bool = False, track_targets: bool = True):
+                  params: Optional[BCEDiceParams] = None, validate: bool = False, track_targets: bool = True,
+                  pixel_weight: Optional[torch.Tensor] = None):
     """Sigmoid BCE + soft Dice: logits [N,K,H,W] (K = 1..3, N <= 64), target [N,H,W] ->
     w_bce BCE + w_dice (1/N) sum_n dice_n (params: None = make_bce_dice_params()); parts [N,2] =
     (bce_n, dice_n).  Pixels at ignore_index count nowhere; other invalid targets count nowhere either
-    and are reported by check_targets() (at once with validate=True)."""
-    loss, parts = BCEDiceFunction.apply(logits, target, params, track_targets)
+    and are reported by check_targets() (at once with validate=True).  pixel_weight (float32 [N,H,W]) multiplies
+    bce(x,t)_c in BCE and bce_n; the denominators and the Dice terms are untouched and it takes no gradient."""
+    if pixel_weight is None:
+        loss, parts = BCEDiceFunction.apply(logits, target, params, track_targets)
+    else:
+        if logits.dim() != 4:
+            raise ValueError(f"expected [N, K, H, W] logits, got {tuple(logits.shape)}")
+        if target.shape != logits.shape[:1] + logits.shape[2:]:
+            raise ValueError(f"target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+        _check_pixel_weight(pixel_weight, logits, target, "bce_dice_loss")
+        loss, parts = WeightedBCEDiceFunction.apply(logits, target, pixel_weight, params, track_targets)
     if validate:
         check_targets()
     return (loss, parts) if return_parts else loss
@@ -318,8 +420,8 @@ class BCEDiceLoss(nn.Module):
                 p.target_mode = _lib.BCE_TARGET_FOREGROUND if num_classes == 1 else _lib.BCE_TARGET_ONEHOT
         return p
 
-    def forward(self, logits, target):
-        return bce_dice_loss(logits, target, params=self.params(logits.shape[1]))
+    def forward(self, logits, target, pixel_weight=None):
+        return bce_dice_loss(logits, target, params=self.params(logits.shape[1]), pixel_weight=pixel_weight)
 
 
 def _as_pixels(inputs: torch.Tensor, targets: torch.Tensor):

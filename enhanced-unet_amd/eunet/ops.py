@@ -407,6 +407,19 @@ def loss_bwd(logits, target, params, sums, gloss, glogits):
          _ptr(glogits), _stream())
 
 
+def loss_fwd_w(logits, target, pixel_weight, params, sums, loss, parts, ws):
+    """eunet_loss_fwd_w: loss_fwd with the focal summand multiplied by pixel_weight [N,H,W] fp32."""
+    n, k, h, w = logits.shape
+    call("eunet_loss_fwd_w", _ptr(logits), _ptr(target), _ptr(pixel_weight), n, k, h, w, _ref(params), _ptr(sums),
+         _ptr(loss), _ptr(parts), _ptr(ws), _stream())
+
+
+def loss_bwd_w(logits, target, pixel_weight, params, sums, gloss, glogits):
+    n, k, h, w = logits.shape
+    call("eunet_loss_bwd_w", _ptr(logits), _ptr(target), _ptr(pixel_weight), n, k, h, w, _ref(params), _ptr(sums),
+         _ptr(gloss), _ptr(glogits), _stream())
+
+
 # ---- sigmoid BCE + Dice loss (bce_dice.hip) ------------------------------------------------
 def bce_dice_default_params() -> _lib.BCEDiceParams:
     p = _lib.BCEDiceParams()
@@ -480,6 +493,112 @@ def bce_dice_fwd(logits, target, params, sums, loss, parts, ws):
 def bce_dice_bwd(logits, target, params, sums, gloss, glogits):
     """torch.ops.eunet.bce_dice_bwd: glogits = gloss * d loss / d logits from the forward's sums."""
     _bce_dice_bwd_op(logits, target, *_bce_flat(params), sums, gloss, glogits)
+
+
+@_dispatched("T T T f f f f f f f f f f f f i i T! T! T! T!")
+def bce_dice_fwd_w(logits, target, pixel_weight, pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth,
+                   ignore_index, target_mode, sums, loss, parts, ws):
+    n, k, h, w = logits.shape
+    prm = _bce_struct((pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth, ignore_index,
+                       target_mode))
+    call("eunet_bce_dice_fwd_w", _ptr(logits), _ptr(target), _ptr(pixel_weight), n, k, h, w, ctypes.byref(prm),
+         _ptr(sums), _ptr(loss), _ptr(parts), _ptr(ws), _stream())
+
+
+@_dispatched("T T T f f f f f f f f f f f f i i T T T!")
+def bce_dice_bwd_w(logits, target, pixel_weight, pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth,
+                   ignore_index, target_mode, sums, gloss, glogits):
+    n, k, h, w = logits.shape
+    prm = _bce_struct((pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth, ignore_index,
+                       target_mode))
+    call("eunet_bce_dice_bwd_w", _ptr(logits), _ptr(target), _ptr(pixel_weight), n, k, h, w, ctypes.byref(prm),
+         _ptr(sums), _ptr(gloss), _ptr(glogits), _stream())
+
+
+_bce_dice_fwd_w_op, _bce_dice_bwd_w_op = bce_dice_fwd_w, bce_dice_bwd_w
+
+
+def bce_dice_fwd_w(logits, target, pixel_weight, params, sums, loss, parts, ws):
+    """torch.ops.eunet.bce_dice_fwd_w: bce_dice_fwd with bce(x,t)_c multiplied by pixel_weight [N,H,W] fp32."""
+    _bce_dice_fwd_w_op(logits, target, pixel_weight, *_bce_flat(params), sums, loss, parts, ws)
+
+
+def bce_dice_bwd_w(logits, target, pixel_weight, params, sums, gloss, glogits):
+    _bce_dice_bwd_w_op(logits, target, pixel_weight, *_bce_flat(params), sums, gloss, glogits)
+
+
+# ---- U-Net border weight map and instance separation (weightmap.hip) -------------------------
+@_dispatched("T T? f f f f f i T!")
+def border_weight_map(labels, semantic, cw0, cw1, cw2, w0, sigma, radius, out):
+    n, h, w = labels.shape
+    cw = (_lib.c_float * 3)(cw0, cw1, cw2)
+    call("eunet_border_weight_map", _ptr(labels), _ptr(semantic), n, h, w, ctypes.byref(cw), w0, sigma, radius,
+         _ptr(out), _stream())
+
+
+_border_weight_map_op = border_weight_map  # torch.ops.eunet.border_weight_map writes into out; the function below allocates it
+
+
+def _label_maps(what, labels, semantic):
+    """labels / semantic as contiguous int64 [N,H,W] device tensors ([H,W] is N = 1) and whether a batch axis was added."""
+    if labels.dim() not in (2, 3):
+        raise ValueError(f"{what}: labels must be [H, W] or [N, H, W], got {tuple(labels.shape)}")
+    if labels.dtype != torch.int64:
+        raise ValueError(f"{what}: labels must be int64, got {labels.dtype}")
+    if semantic is not None and (semantic.dtype != torch.int64 or semantic.shape != labels.shape or
+                                 semantic.device != labels.device):
+        raise ValueError(f"{what}: semantic must be int64 of labels' shape {tuple(labels.shape)} on its device")
+    squeeze = labels.dim() == 2
+    lb = labels.contiguous()
+    sm = None if semantic is None else semantic.contiguous()
+    if squeeze:
+        lb, sm = lb.unsqueeze(0), None if sm is None else sm.unsqueeze(0)
+    return lb, sm, squeeze
+
+
+def border_weight_map(labels, semantic=None, *, class_weight=(1.0, 1.0, 1.0), w0: float = 10.0, sigma: float = 5.0,
+                      radius=None, out=None):
+    """The U-Net border weight map (include/eunet.h, eunet_border_weight_map): labels int64 [N,H,W] or [H,W]
+    (0 background, anything else an instance id), semantic (optional, same shape) -> float32 of labels' shape,
+    class_weight[semantic] + w0 exp(-(d1 + d2)^2 / (2 sigma^2)) on background pixels with two distinct ids inside
+    the square window of radius R (None: ceil(5.5 sigma); 1 <= R <= 48)."""
+    lb, sm, squeeze = _label_maps("border_weight_map", labels, semantic)
+    cw = [float(c) for c in class_weight]
+    if len(cw) != 3:
+        raise ValueError(f"border_weight_map: class_weight needs 3 values, got {len(cw)}")
+    if not float(sigma) > 0.0 or not float(w0) >= 0.0:
+        raise ValueError(f"border_weight_map: needs sigma > 0 and w0 >= 0, got sigma {sigma}, w0 {w0}")
+    r = _lib.WMAP_RADIUS_AUTO if radius is None else int(radius)
+    if radius is not None and not 1 <= r <= _lib.WMAP_MAX_RADIUS:
+        raise ValueError(f"border_weight_map: radius {radius} outside 1..{_lib.WMAP_MAX_RADIUS}")
+    if out is None:
+        out = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)
+    elif out.dtype != torch.float32 or out.shape != labels.shape or not out.is_contiguous() or out.device != labels.device:
+        raise ValueError("border_weight_map: out must be a contiguous float32 tensor of labels' shape on its device")
+    _border_weight_map_op(lb, sm, cw[0], cw[1], cw[2], float(w0), float(sigma), r, out.unsqueeze(0) if squeeze else out)
+    return out
+
+
+@_dispatched("T T? T! T!?")
+def separate_instances(labels, semantic, labels_out, semantic_out):
+    n, h, w = labels.shape
+    call("eunet_separate_instances", _ptr(labels), _ptr(semantic), n, h, w, _ptr(labels_out), _ptr(semantic_out),
+         _stream())
+
+
+_separate_instances_op = separate_instances
+
+
+def separate_instances(labels, semantic=None):
+    """eunet_separate_instances: a pixel whose 3x3 neighbourhood holds another instance's label becomes background
+    in labels and in semantic, so both sides of a contact lose one pixel -> (labels', semantic' or None)."""
+    lb, sm, squeeze = _label_maps("separate_instances", labels, semantic)
+    lo = torch.empty_like(lb)
+    so = None if sm is None else torch.empty_like(sm)
+    _separate_instances_op(lb, sm, lo, so)
+    if squeeze:
+        lo, so = lo[0], None if so is None else so[0]
+    return lo, so
 
 
 def bn_bwd_tiles(y: Act) -> int:

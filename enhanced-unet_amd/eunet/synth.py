@@ -5,6 +5,8 @@ x in [0,1]: smooth illumination field + Poisson(H*W/4000) elliptical cells
 mask: 0 background / 1 cell (K=2) or 1 live / 2 dead with p 0.7 / 0.3 (K=3).
 Seeded per global sample index (seed = 1000 + index), generated on the host
 once and moved to the device (the benchmark keeps them resident in HBM).
+tile(..., instances=True) also returns the instance label map (cell j of the tile's draw order has id
+j + 1, later cells overwrite earlier ones as in the mask): what ops.border_weight_map reads.
 """
 from __future__ import annotations
 
@@ -12,14 +14,15 @@ import numpy as np
 import torch
 
 
-def tile(h: int, w: int, index: int, num_classes: int = 2, in_channels: int = 1):
+def tile(h: int, w: int, index: int, num_classes: int = 2, in_channels: int = 1, instances: bool = False):
     rng = np.random.default_rng(1000 + index)
     yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
     fx, fy, ph = rng.uniform(0.5, 2.0), rng.uniform(0.5, 2.0), rng.uniform(0, 2 * np.pi)
     img = 0.55 + 0.12 * np.sin(2 * np.pi * fx * xx / w + ph) * np.cos(2 * np.pi * fy * yy / h)
     mask = np.zeros((h, w), np.int64)
+    inst = np.zeros((h, w), np.int64) if instances else None
     ncell = rng.poisson(h * w / 4000.0)
-    for _ in range(ncell):
+    for j in range(ncell):
         cy, cx = rng.uniform(0, h), rng.uniform(0, w)
         ra, rb = rng.uniform(4, 14), rng.uniform(4, 14)
         th = rng.uniform(0, np.pi)
@@ -38,9 +41,13 @@ def tile(h: int, w: int, index: int, num_classes: int = 2, in_channels: int = 1)
         img[y0:y1, x0:x1] -= 0.18 * halo
         img[y0:y1, x0:x1] += 0.25 * np.clip(1.0 - d / 0.8, 0.0, 1.0) * (0.6 if cls == 2 else 1.0)
         mask[y0:y1, x0:x1][inside] = cls
+        if instances:
+            inst[y0:y1, x0:x1][inside] = j + 1
     img += rng.normal(0.0, 0.03, size=(h, w))
     img = np.clip(img, 0.0, 1.0).astype(np.float32)
     x = np.repeat(img[None], in_channels, axis=0)
+    if instances:
+        return x, mask, inst
     return x, mask
 
 

@@ -333,6 +333,62 @@ int eunet_bce_dice_bwd(const float* logits, const int64_t* target, int n, int k,
                        const eunet_bce_dice_params* params, const float* sums, const float* gloss, float* glogits,
                        void* stream);
 
+/* ---- U-Net border weight map, instance separation, pixel-weighted losses (weightmap.hip) ----
+ * No reference line to cite: the reference fills its polygons into one 0/1/2 mask and weights a pixel by
+ * its class only.  The map is the per-pixel weight of Ronneberger et al., "U-Net" (2015), eq. 2; this
+ * comment is the definition.
+ *
+ * labels [N,H,W] int64: 0 is background, any other value an instance id.  Ids need not be contiguous and
+ * may exceed 16 bits; the same id in two separate places is one instance.  The kernel tells ids apart by
+ * their low 32 bits (every id in [1, 2^32) is safe; an id whose low 32 bits are 0 would read as
+ * background).  semantic (nullable) [N,H,W] int64.
+ *
+ * Distances.  For a pixel x of sample n and an id i, over the pixels q of that sample with labels(q) = i,
+ * |qx - xx| <= R and |qy - xy| <= R (a square window, inclusive, cut at the image edge, never wrapped):
+ *   d_i(x) = min ||x - q||  (Euclidean);  d1 <= d2 = the two smallest d_i(x) over DISTINCT ids.
+ *   border(x) = w0 exp(-(d1 + d2)^2 / (2 sigma^2))  where labels(x) = 0 and two distinct ids lie in the window
+ *   border(x) = 0                                   elsewhere: cell pixels, background with < 2 ids in reach
+ *   base(x)   = class_weight[semantic(x)] when semantic is given and its value is 0, 1 or 2, else 1
+ *   out(x)    = base(x) + border(x)
+ * radius R: EUNET_WMAP_RADIUS_AUTO = ceil(5.5 sigma).  sigma > 0, w0 >= 0 and 1 <= R <= 48 are required,
+ * anything else is EUNET_ERR_INVALID.  class_weight: 3 host floats (nullable = 1, 1, 1).
+ * The window is part of the definition, not an approximation: where the untruncated map (R = infinity)
+ * differs from this one, a distance beyond R is involved, so d1 + d2 > R and both border terms are below
+ * w0 exp(-R^2 / (2 sigma^2)) -- at the default R that is 2.7e-7 w0.
+ * No host synchronisation, no allocation; enqueued on stream only. */
+#define EUNET_WMAP_RADIUS_AUTO (-1)
+int eunet_border_weight_map(const int64_t* labels, const int64_t* semantic, int n, int h, int w,
+                            const float* class_weight, float w0, float sigma, int radius, float* out,
+                            void* stream);
+/* The usual companion of the map, exact integer work (ids compared in all 64 bits):
+ *   labels'(x) = 0 and semantic'(x) = 0 where some pixel of the 3x3 neighbourhood of x, inside the image,
+ *   has a label that is neither 0 nor labels(x); every other pixel is unchanged.
+ * Both outputs are computed from the inputs (not in place: the outputs must not alias the inputs), so both
+ * sides of a contact lose one pixel.  semantic and semantic_out are both given or both null. */
+int eunet_separate_instances(const int64_t* labels, const int64_t* semantic, int n, int h, int w,
+                             int64_t* labels_out, int64_t* semantic_out, void* stream);
+/* eunet_loss_fwd / _bwd with a per-pixel weight m = pixel_weight [N,H,W] fp32 (non-null; it takes no
+ * gradient): the per-pixel focal summand alpha_t (1 - pt)^gamma ce is multiplied by m(x), F_den stays
+ * N*H*W, Dice and Tversky are untouched; ignored and out-of-range pixels contribute as in eunet_loss_fwd
+ * (nothing to the focal term, whatever their weight).  focal_norm = 1 is EUNET_ERR_INVALID here: its
+ * denominator would need a definition of its own.  The logit gradient gets the factor m(x) on its focal
+ * part only.  sums / ws layouts are eunet_loss_fwd's; m = 1 everywhere gives eunet_loss_fwd's bits. */
+int eunet_loss_fwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k,
+                     int h, int w, const eunet_loss_params* params, float* sums, float* loss, float* parts,
+                     void* ws, void* stream);
+int eunet_loss_bwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k,
+                     int h, int w, const eunet_loss_params* params, const float* sums, const float* gloss,
+                     float* glogits, void* stream);
+/* eunet_bce_dice_fwd / _bwd with a per-pixel weight m (as above): bce(x,t)_c is multiplied by m(x), in BCE
+ * and in bce_n; the denominators K max(1, V) and the Dice terms are untouched, so m = 1 is the unweighted
+ * loss, bit for bit.  The logit gradient gets the factor m(x) on its BCE part only. */
+int eunet_bce_dice_fwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k,
+                         int h, int w, const eunet_bce_dice_params* params, float* sums, float* loss,
+                         float* parts, void* ws, void* stream);
+int eunet_bce_dice_bwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k,
+                         int h, int w, const eunet_bce_dice_params* params, const float* sums,
+                         const float* gloss, float* glogits, void* stream);
+
 /* ---- backward helpers ----------------------------------------------------
  * BN(+ReLU) backward (autograd of models.py:220-224): g is the gradient w.r.t.
  * the ReLU output, y the pre-BN conv output, mean / invstd the batch statistics and
