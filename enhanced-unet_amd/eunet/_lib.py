@@ -141,6 +141,9 @@ SIGNATURES = {
     "eunet_probs_to_mask": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
     "eunet_sigmoid_crop": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_probs_threshold": [_f, c_int, c_int, c_int, c_float, _f, c_void_p],
+    "eunet_tile_gather": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
+    "eunet_tile_blend": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, _f, c_int,
+                         c_int, c_int, _f, c_void_p],
     "eunet_pack_masks": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
     "eunet_pack_masks_bbox": [_f, c_int, c_int, c_int, _f, _f, _f, c_void_p],
     "eunet_coco_match": [_f, _f, _f, _f, _f, _f, _f, c_int, c_int, POINTER(ctypes.c_double), c_int, _f, c_void_p],

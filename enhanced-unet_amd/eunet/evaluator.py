@@ -3,6 +3,7 @@
     Evaluator(model, device, model_name)                       # train_eval.py:356-363
     ._run_model_single(image [C,h,w]) -> probs [K,h,w]          # train_eval.py:397-417
     ._run_tta_inference(image) -> probs (5-view TTA mean)       # train_eval.py:419-453
+    .predict_probs(image) -> probs [K,h,w] on the device (what predict_semantic_mask converts)
     ._convert_probs_to_mask(probs) -> int64 mask [h,w] (numpy)  # train_eval.py:455-568
     .predict_semantic_mask(image) -> int64 mask [h,w] (numpy)   # train_eval.py:570-606
     .semantic_to_instances(mask, min_area=3)                    # train_eval.py:654-850
@@ -40,6 +41,13 @@ on the device (eunet_pack_masks_bbox, eunet_pairwise_overlap,
 eunet_coco_match); only the match tables come back, and
 metrics.coco_map_from_matches accumulates them once at the end.  The default
 evaluate() returns the 23 EVALUATE_KEYS rows as before.
+
+Overlap-tile inference (no reference counterpart: the reference resizes every image down to max_size):
+Evaluator(..., tile=T) sends an image whose padded size exceeds T in either axis through the network tile by
+tile (eunet.tiling.plan; ops.tile_gather, forward_lowres on tile_batch tiles at a time, one ops.tile_blend
+with the activation and the flips) and everything above _run_model_single runs unchanged on the full-size
+probabilities.  With the default blend "crop" and margin (tiling.RECEPTIVE_MARGIN) the probabilities are the
+whole-image forward's, bit for bit (tests/test_gpu_tiling.py).
 """
 from __future__ import annotations
 
@@ -51,7 +59,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, tiling
 from .metrics import (calculate_dice, calculate_instance_metrics, calculate_iou, calculate_semantic_metrics,
                       calculate_viability_metrics, coco_image_matches, coco_map_from_matches)
 
@@ -92,8 +100,16 @@ def reference_preprocess(image: torch.Tensor) -> torch.Tensor:
 
 class Evaluator:
     def __init__(self, model, device, model_name, preprocess: Union[str, Callable, None] = "reference", *,
-                 activation: str = "softmax", threshold: float = 0.5):
-        """activation "softmax" is the reference's path.  "sigmoid" is the prediction path of a model trained
+                 activation: str = "softmax", threshold: float = 0.5, tile: Optional[int] = None,
+                 tile_blend: str = "crop", tile_margin: Optional[int] = None, tile_overlap: float = 0.25,
+                 tile_batch: int = 4):
+        """tile: None (one forward per view, as the reference) or the largest tile side, a multiple of 32: a
+        view whose padded height or width exceeds it is predicted tile by tile (eunet.tiling.plan with blend
+        tile_blend, margin tile_margin for "crop" -- None: tiling.RECEPTIVE_MARGIN, for which the result is
+        exact -- and tile_overlap for "constant" / "gaussian"), tile_batch tiles per forward.  Not for a
+        dual-branch model: its fusion head widens the receptive field, which has not been measured.
+
+        activation "softmax" is the reference's path.  "sigmoid" is the prediction path of a model trained
         with losses.bce_dice_loss: a sigmoid per logit (ops.sigmoid_crop), the same TTA mean of probabilities,
         then ops.probs_threshold ([p >= threshold] for one logit, the argmax for more); the reference's
         hand-tuned probs_to_mask rules are softmax-specific and are not applied."""
@@ -106,6 +122,22 @@ class Evaluator:
         self.model_name = model_name
         self.enable_tta = model_name == "enhanced_unet"
         self.preprocess = preprocess
+        self.tile = None if tile is None else int(tile)
+        self.tile_blend, self.tile_margin, self.tile_overlap = tile_blend, tile_margin, float(tile_overlap)
+        self.tile_batch = int(tile_batch)
+        if self.tile is not None:
+            if getattr(model, "dual_branch", False):
+                raise ValueError("tile: tiled inference is not built for the dual-branch model (the receptive "
+                                 "margin of its fusion head has not been measured)")
+            if self.tile_batch < 1:
+                raise ValueError(f"tile_batch must be at least 1, not {tile_batch}")
+            if not hasattr(model, "forward_lowres"):
+                raise ValueError("tile: tiled inference needs a model with forward_lowres")
+            self._tile_plan(self.tile, self.tile)  # the plan's refusals (tile, blend, margin, overlap) at construction
+
+    def _tile_plan(self, h: int, w: int) -> tiling.TilePlan:
+        return tiling.plan(h, w, self.tile, blend=self.tile_blend, margin=self.tile_margin,
+                           overlap=self.tile_overlap)
 
     # ---- train_eval.py:365-395 -------------------------------------------------
     def _prepare_image_tensor(self, image: torch.Tensor) -> torch.Tensor:
@@ -131,6 +163,8 @@ class Evaluator:
         probabilities back (the TTA flips of train_eval.py:427-437)."""
         h, w = image.shape[1:]
         h_pad, w_pad = (32 - h % 32) % 32, (32 - w % 32) % 32
+        if self.tile is not None and (h + h_pad > self.tile or w + w_pad > self.tile):
+            return self._run_model_tiled(image, flip_h, flip_w)
         x = image.unsqueeze(0)
         if h_pad or w_pad:
             x = F.pad(x, (0, w_pad, 0, h_pad), mode="reflect")
@@ -138,6 +172,20 @@ class Evaluator:
         if self.activation == "sigmoid":
             return ops.sigmoid_crop(logits, h, w, flip_h=flip_h, flip_w=flip_w)
         return ops.softmax_crop(logits, h, w, flip_h=flip_h, flip_w=flip_w)
+
+    def _run_model_tiled(self, image: torch.Tensor, flip_h: bool, flip_w: bool) -> torch.Tensor:
+        """_run_model_single for a view larger than self.tile: gather tile_batch tiles at a time, forward_lowres
+        on the batch into one [N,K,th,tw] buffer, one blend with the activation and the flips."""
+        image = image.contiguous().float()
+        p = self._tile_plan(*image.shape[1:])
+        logits = None
+        for first in range(0, p.n, self.tile_batch):
+            count = min(self.tile_batch, p.n - first)
+            out = self.model.forward_lowres(ops.tile_gather(image, p, first, count))
+            if logits is None:
+                logits = torch.empty(p.n, out.shape[1], p.th, p.tw, dtype=torch.float32, device=image.device)
+            logits[first:first + count].copy_(out)
+        return ops.tile_blend(logits, p, self.activation, flip_h=flip_h, flip_w=flip_w)
 
     # ---- train_eval.py:419-453 -------------------------------------------------
     def _run_tta_inference(self, image: torch.Tensor) -> torch.Tensor:
@@ -174,13 +222,18 @@ class Evaluator:
             mask = mask[:h_orig, :w_orig]
         return mask.cpu().numpy()
 
-    def predict_semantic_mask(self, image: torch.Tensor) -> np.ndarray:
+    def predict_probs(self, image: torch.Tensor) -> torch.Tensor:
+        """image [C,h,w] -> the probabilities [K,h,w] on the device that predict_semantic_mask converts (the TTA
+        mean for 'enhanced_unet', one view otherwise; tiled where the evaluator's tile says so)."""
         self.model.eval()
         with torch.no_grad():
             x = self._prepare_image_tensor(image)
             if self.model_name == "enhanced_unet":
-                return self._convert_probs_to_mask(self._run_tta_inference(x))
-            return self._convert_probs_to_mask(self._run_model_single(x))
+                return self._run_tta_inference(x)
+            return self._run_model_single(x)
+
+    def predict_semantic_mask(self, image: torch.Tensor) -> np.ndarray:
+        return self._convert_probs_to_mask(self.predict_probs(image))
 
     def evaluate_semantic(self, dataloader) -> Dict[str, float]:
         """Mean of calculate_semantic_metrics over the images (the semantic rows of evaluate())."""

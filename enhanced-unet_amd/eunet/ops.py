@@ -880,6 +880,88 @@ def probs_threshold(probs, threshold: float = 0.5):
     return mask
 
 
+# ---- overlap-tile inference (tiling.hip; the geometry is eunet.tiling.TilePlan) ----------
+TILE_ACTIVATIONS = {"none": 0, "softmax": 1, "sigmoid": 2}  # EUNET_TILE_ACT_*
+
+
+@_dispatched("T i i i i i i i i T!")
+def tile_gather(image, hp, wp, th, tw, sy, sx, first, count, out):
+    c, h, w = image.shape
+    with kprof.timed("tile_gather", 0.0, 8.0 * out.numel()):
+        call("eunet_tile_gather", _ptr(image), c, h, w, hp, wp, th, tw, sy, sx, first, count, _ptr(out), _stream())
+
+
+_tile_gather_op = tile_gather  # torch.ops.eunet.tile_gather takes the geometry as integers and writes into out
+
+
+def _plan_of(name, plan, h, w):
+    if (plan.h, plan.w) != (h, w):
+        raise ValueError(f"{name}: the plan is for a {plan.h} x {plan.w} image, not {h} x {w}")
+
+
+def tile_gather(image, plan, first: int = 0, count: int | None = None, out=None):
+    """image [C, h, w] fp32 (C = 1..4) -> tiles [count, C, th, tw]: tile numbers first .. first + count - 1 of
+    plan (eunet.tiling.plan) cut from the image as reflect-padded to plan.hp x plan.wp; no padded copy is made."""
+    if image.dim() != 3:
+        raise ValueError(f"tile_gather: image must be [C, h, w], got {tuple(image.shape)}")
+    image = image.contiguous().float()
+    c, h, w = image.shape
+    _plan_of("tile_gather", plan, h, w)
+    count = plan.n - first if count is None else int(count)
+    if first < 0 or count < 1 or first + count > plan.n:
+        raise ValueError(f"tile_gather: tiles {first} .. {first + count - 1} are not inside the plan's {plan.n}")
+    shape = (count, c, plan.th, plan.tw)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=image.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"tile_gather: out must be a contiguous fp32 {shape}, got {tuple(out.shape)} {out.dtype}")
+    _tile_gather_op(image, plan.hp, plan.wp, plan.th, plan.tw, plan.stride, plan.stride, int(first), count, out)
+    return out
+
+
+@_dispatched("T i i i i i i i i i i T? T? i b b T!")
+def tile_blend(logits, h, w, hp, wp, th, tw, sy, sx, mode, margin, wy, wx, activation, flip_h, flip_w, out):
+    k = logits.shape[1]
+    # per output pixel: K floats written, and K floats read per covering tile (logits.numel() in all)
+    with kprof.timed("tile_blend", 0.0, 4.0 * (logits.numel() + out.numel())):
+        call("eunet_tile_blend", _ptr(logits), k, h, w, hp, wp, th, tw, sy, sx, mode, margin, _ptr(wy), _ptr(wx),
+             activation, int(flip_h), int(flip_w), _ptr(out), _stream())
+
+
+_tile_blend_op = tile_blend
+_tile_tables: dict = {}  # (device, th, tw, sigma_scale) -> the gaussian tables (wy, wx) on that device
+
+
+def _gauss_tables(plan, device):
+    key = (str(device), plan.th, plan.tw, plan.sigma_scale)
+    if key not in _tile_tables:
+        if len(_tile_tables) >= 16:
+            _tile_tables.clear()
+        _tile_tables[key] = tuple(torch.from_numpy(plan.table(a)).to(device) for a in (0, 1))
+    return _tile_tables[key]
+
+
+def tile_blend(logits, plan, activation: str = "softmax", flip_h=False, flip_w=False, out=None):
+    """tile logits [plan.n, K, th, tw] fp32 (K = 1..3) -> probs [K, h, w]: per pixel the weighted mean, over
+    the tiles that cover it in increasing tile number, of activation ('softmax' over K, 'sigmoid' or 'none')
+    of the tile's logits, with plan.blend's weights; cropped to h x w, softmax_crop's flips on the destination."""
+    if activation not in TILE_ACTIVATIONS:
+        raise ValueError(f"tile_blend: activation must be one of {tuple(TILE_ACTIVATIONS)}, not {activation!r}")
+    if logits.dim() != 4 or tuple(logits.shape[2:]) != (plan.th, plan.tw) or logits.shape[0] != plan.n:
+        raise ValueError(f"tile_blend: logits must be [{plan.n}, K, {plan.th}, {plan.tw}], got {tuple(logits.shape)}")
+    logits = logits.contiguous().float()
+    k = logits.shape[1]
+    shape = (k, plan.h, plan.w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=logits.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"tile_blend: out must be a contiguous fp32 {shape}, got {tuple(out.shape)} {out.dtype}")
+    wy, wx = _gauss_tables(plan, logits.device) if plan.blend == "gaussian" else (None, None)
+    _tile_blend_op(logits, plan.h, plan.w, plan.hp, plan.wp, plan.th, plan.tw, plan.stride, plan.stride, plan.mode,
+                   plan.margin, wy, wx, TILE_ACTIVATIONS[activation], bool(flip_h), bool(flip_w), out)
+    return out
+
+
 # ---- instance-level evaluation (instances.hip) -----------------------------------------
 MORPH_ELEMS = {2: 0, 3: 1, 5: 2}  # side of cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)) -> eunet_morph_u8 elem
 

@@ -419,7 +419,7 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
  * eunet_debug_enabled: 1 in the debug build, 0 in the release library (where the checks compile away).
  * eunet_debug_status: synchronises the device; *count = failed checks since the last reset,
  * *unit_line = unit * 100000 + source line of the first (units: 1 capi, 2 conv3x3, 3 bn_pool_up,
- * 4 head, 5 instances, 6 baselines, 7 upconv; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
+ * 4 head, 5 instances, 6 baselines, 7 upconv, 8 bce_dice, 9 weightmap, 10 tiling; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
 int eunet_debug_enabled(void);
 int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset);
 int eunet_debug_selftest(void* stream);
@@ -531,6 +531,43 @@ int eunet_sigmoid_crop(const float* logits, int k, int hp, int wp, int h, int w,
                        int flip_w, float* probs, void* stream);
 int eunet_probs_threshold(const float* probs, int k, int h, int w, float threshold, int64_t* mask,
                           void* stream);
+
+/* ---- overlap-tile inference (tiling.hip) -------------------------------------
+ * Prediction on an image larger than one forward pass (no reference line: the reference's only answer to a
+ * large field of view is the resize down to max_size, dataset.py; overlap-tile prediction is the strategy
+ * of the U-Net paper, Ronneberger et al. 2015, section 2).  The image [C][h][w] is extended to hp x wp = h, w rounded up to
+ * multiples of 32 by the reflect pad to the bottom / right of train_eval.py:397-417 (position r >= n reads
+ * 2 (n - 1) - r; hp - h < h and wp - w < w, as F.pad demands) and cut into ny x nx tiles of th x tw pixels
+ * (multiples of 32, th <= hp, tw <= wp).  Along an axis of padded length L, tile extent e and stride S (a
+ * positive multiple of 32): n = 1 if L <= e else ceil((L - e) / S) + 1 tiles with origins
+ * o(i) = min(i S, L - e); tile number = iy * nx + ix.  The geometry is passed by value and the counts are
+ * derived from it; every offset is 64-bit.
+ * eunet_tile_gather: tiles [count][C][th][tw] (16-byte aligned) = tile numbers first .. first + count - 1
+ * of the extended image, read through the reflect index (no padded copy is made); C = 1..4.
+ * eunet_tile_blend: tile logits [ny nx][K][th][tw] (K = 1..3, 16-byte aligned) -> probs [K][h][w],
+ *   probs[k][y'][x'] = sum_n w_n act(logits_n)[k] / sum_n w_n  over the tiles n that cover (y, x), summed in
+ * increasing tile number in fp32 (one thread per pixel: deterministic, no atomics), cropped to h x w, with
+ * y' = flip_h ? h - 1 - y : y and x' likewise (eunet_softmax_crop's flips).  act: EUNET_TILE_ACT_NONE, _SOFTMAX
+ * (over K, eunet_softmax_crop's arithmetic) or _SIGMOID (eunet_sigmoid_crop's).  w_n = wy(ty) wx(tx) at the
+ * tile-local position; per axis, for a tile at origin o:
+ *   EUNET_TILE_CROP      1 if (o > 0 ? margin : 0) <= t < e - (o + e < L ? margin : 0) else 0; margin a
+ *                        multiple of 16 with S + 2 margin <= e wherever an axis has more than one tile
+ *   EUNET_TILE_CONSTANT  1 (S <= e)
+ *   EUNET_TILE_GAUSSIAN  wy[t] / wx[t]: device tables of th / tw floats (wx 16-byte aligned); null otherwise
+ * In crop mode at most two cores overlap per axis, so sum w is 1, 2 or 4 and the mean of bit-equal tile
+ * values is exact: with margin >= the network's receptive radius (eunet.tiling.RECEPTIVE_MARGIN) the result
+ * is the whole-image forward's, bit for bit. */
+#define EUNET_TILE_CROP 0
+#define EUNET_TILE_CONSTANT 1
+#define EUNET_TILE_GAUSSIAN 2
+#define EUNET_TILE_ACT_NONE 0
+#define EUNET_TILE_ACT_SOFTMAX 1
+#define EUNET_TILE_ACT_SIGMOID 2
+int eunet_tile_gather(const float* image, int c, int h, int w, int hp, int wp, int th, int tw, int sy,
+                      int sx, int first, int count, float* tiles, void* stream);
+int eunet_tile_blend(const float* logits, int k, int h, int w, int hp, int wp, int th, int tw, int sy,
+                     int sx, int mode, int margin, const float* wy, const float* wx, int activation,
+                     int flip_h, int flip_w, float* probs, void* stream);
 
 /* ---- instance-level evaluation (instances.hip) ------------------------------
  * Pairwise mask overlap (metrics.py:61-194, calculate_instance_metrics: the calculate_iou
