@@ -115,6 +115,9 @@ SIGNATURES = {
     "eunet_loss_bwd_w": [_f, _f, _f, c_int, c_int, c_int, c_int, POINTER(LossParams), _f, _f, _f, c_void_p],
     "eunet_bce_dice_fwd_w": [_f, _f, _f, c_int, c_int, c_int, c_int, POINTER(BCEDiceParams), _f, _f, _f, _f, c_void_p],
     "eunet_bce_dice_bwd_w": [_f, _f, _f, c_int, c_int, c_int, c_int, POINTER(BCEDiceParams), _f, _f, _f, c_void_p],
+    "eunet_warp_grid": [_f, c_int, c_int, POINTER(ctypes.c_double * 6), c_int, c_int, _f, c_void_p],
+    "eunet_warp_u8": [_f, c_int, c_int, c_int, _f, c_int, c_int, c_int, c_int, _f, c_void_p],
+    "eunet_warp_labels": [_f, c_int, c_int, c_int, c_int, _f, c_int, c_int, c_int, c_int64, c_int, c_int, _f, c_void_p],
     "eunet_bn_bwd_tiles": [_P, POINTER(c_int)],
     "eunet_bn_bwd_reduce": [_P, _P, _f, _f, _f, _f, _f, c_void_p],
     "eunet_colsum_ws_bytes": [c_int, c_int, POINTER(c_size_t)],

@@ -35,6 +35,15 @@ Python `random` draws stay in item order (one producer thread).
 CellDataset(..., weight_map={...}) (not in the reference): every item also carries the U-Net border
 weight map of its polygons (ops.border_weight_map, include/eunet.h) and the instance label map it was
 computed from; it draws no random number, so the augmentation stream is the one of weight_map=None.
+
+CellDataset(..., elastic={...}) (not in the reference; U-Net paper §3.1): every training item is first moved
+geometrically -- a random rotation and scale about the image centre plus random displacements on a coarse
+control grid, interpolated bicubically (ops.elastic_grid) -- image (bilinear, ops.warp_u8) and every label
+(nearest, ops.warp_labels) through one map, before the photometric augmentations.  Its draws come from a
+generator of the dataset's own, so `random` and `np.random` see the stream of elastic=None.  Consequences:
+`bboxes` stay in the unwarped, unflipped frame (they already ignore the flips); `instance_labels` keeps its
+length even when a cell leaves the frame (its mask is then empty); with border="reflect" a mirrored copy of a
+cell at the image edge keeps the cell's id; the weight map is computed from the warped ids, never interpolated.
 """
 from __future__ import annotations
 
@@ -88,6 +97,17 @@ def load_labelme(json_path: str, scale_h: float, scale_w: float):
     return polys, labels, bboxes
 
 
+def warp_matrix(h, w, angle_deg, scale):
+    """The float64 2x3 inverse (destination -> source) map of a rotation by angle_deg and a zoom by `scale`
+    about the image centre c = ((w - 1) / 2, (h - 1) / 2): src = c + (1 / scale) R(angle) (dst - c)."""
+    a = np.deg2rad(float(angle_deg))
+    cs, sn = (1.0, 0.0) if float(angle_deg) == 0.0 else (float(np.cos(a)), float(np.sin(a)))
+    k = 1.0 / float(scale)
+    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+    return np.array([[k * cs, -k * sn, cx - k * (cs * cx - sn * cy)],
+                     [k * sn, k * cs, cy - k * (sn * cx + cs * cy)]], dtype=np.float64)
+
+
 def host_load(data_dir, name, max_size):
     """dataset.py:133-195 up to the pixels: JPEG decode (PIL), the /32 target size and the LabelMe
     polygons scaled to it.  Module level, so DataLoader worker processes can run it."""
@@ -107,7 +127,7 @@ def _host_load_args(args):
 class CellDataset:
     def __init__(self, data_dir: str, split: str = "train", transform=None, max_size: int = 1024,
                  device: str = "cuda", cell_preprocess: bool = True, host_noise: bool = True,
-                 host_ratio: bool = False, weight_map=None):
+                 host_ratio: bool = False, weight_map=None, elastic=None):
         self.data_dir, self.split, self.transform, self.max_size = data_dir, split, transform, max_size
         self.device = device
         self.cell_preprocess = cell_preprocess  # dataset.py:204 (always on in the reference)
@@ -121,6 +141,10 @@ class CellDataset:
         self._noise_gen = None
         # weight_map: None (every item exactly as without the feature) or a dict of WEIGHT_MAP_DEFAULTS' keys
         self.weight_map = self._weight_map_config(weight_map)
+        # elastic: None (every item exactly as without the feature) or a dict of ELASTIC_DEFAULTS' keys; its
+        # draws come from a generator of its own, used only in from_host (the main process)
+        self.elastic = self._elastic_config(elastic)
+        self._elastic_rng = None if self.elastic is None else np.random.Generator(np.random.PCG64(self.elastic["seed"]))
         all_files = sorted(f for f in os.listdir(data_dir) if f.endswith(".jpg"))
         n_total = len(all_files)
         n_train, n_val = int(n_total * 0.7), int(n_total * 0.15)
@@ -157,16 +181,73 @@ class CellDataset:
         c["radius"], c["separate"] = r, bool(c["separate"])
         return c
 
-    def _weight_map_item(self, polys, h, w, flips, mask, device):
+    ELASTIC_DEFAULTS = dict(sigma=10.0, grid=3, rotate=0.0, scale=(1.0, 1.0), p=1.0, border="reflect", seed=None)
+
+    @classmethod
+    def _elastic_config(cls, cfg):
+        """The elastic argument checked on the host (ValueError), as _weight_map_config does."""
+        if cfg is None:
+            return None
+        if not isinstance(cfg, dict):
+            raise ValueError(f"elastic must be None or a dict, got {type(cfg).__name__}")
+        unknown = set(cfg) - set(cls.ELASTIC_DEFAULTS)
+        if unknown:
+            raise ValueError(f"elastic: unknown key(s) {sorted(unknown)}; known: {sorted(cls.ELASTIC_DEFAULTS)}")
+        c = dict(cls.ELASTIC_DEFAULTS, **cfg)
+        g = c["grid"]
+        try:
+            gh, gw = (int(g), int(g)) if np.isscalar(g) else (int(g[0]), int(g[1]))
+            if not np.isscalar(g) and len(g) != 2:
+                raise TypeError
+            lo, hi = (float(v) for v in c["scale"])
+            c["sigma"], c["rotate"], c["p"] = float(c["sigma"]), float(c["rotate"]), float(c["p"])
+        except (TypeError, ValueError, IndexError):
+            raise ValueError(f"elastic: needs numbers for sigma, rotate, p, a (lo, hi) scale and an int or (gh, gw) grid, "
+                             f"got {cfg}") from None
+        if not (2 <= gh <= ops.WARP_GRID_MAX and 2 <= gw <= ops.WARP_GRID_MAX):
+            raise ValueError(f"elastic: grid {gh} x {gw} outside 2..{ops.WARP_GRID_MAX}")
+        if not (c["sigma"] >= 0.0 and np.isfinite(c["sigma"])) or not (c["rotate"] >= 0.0 and np.isfinite(c["rotate"])):
+            raise ValueError(f"elastic: needs finite sigma >= 0 and rotate >= 0, got sigma {c['sigma']}, rotate {c['rotate']}")
+        if not 0.0 <= c["p"] <= 1.0:
+            raise ValueError(f"elastic: p {c['p']} outside [0, 1]")
+        if not (0.0 < lo <= hi and np.isfinite(hi)):
+            raise ValueError(f"elastic: scale bounds must satisfy 0 < lo <= hi, got {c['scale']}")
+        if c["border"] not in ops.WARP_BORDERS:
+            raise ValueError(f"elastic: unknown border {c['border']!r}; known: {sorted(ops.WARP_BORDERS)}")
+        c["grid"], c["scale"] = (gh, gw), (lo, hi)
+        return c
+
+    def _elastic_draw(self, h, w, device):
+        """The sampling map of the next training item (float32 [h, w, 2] on the device), or None when the p draw
+        skips the item.  Draw order: u, angle, scale, control displacements -- made even when a range is
+        degenerate, from the dataset's own generator (`random` / `np.random` are not touched)."""
+        c, rng = self.elastic, self._elastic_rng
+        if rng.random() >= c["p"]:
+            return None
+        angle = rng.uniform(-c["rotate"], c["rotate"])
+        s = rng.uniform(*c["scale"])
+        ctrl = rng.normal(0.0, c["sigma"], (2,) + c["grid"])
+        return ops.elastic_grid(h, w, ctrl, warp_matrix(h, w, angle, s), device)
+
+    def _warp(self, img, mask, grid):
+        """The geometric stage: image (bilinear) and semantic mask (nearest) through one map."""
+        b = self.elastic["border"]
+        return ops.warp_u8(img, grid, border=b), ops.warp_labels(mask, grid, border=b)
+
+    def _weight_map_item(self, polys, h, w, flips, mask, device, grid=None):
         """(semantic mask, weight map, instance label map) of one item: polygon i filled with id i + 1 by the
         semantic mask's own rasteriser (later polygons overwrite earlier ones, as there), mirrored by the flips
-        _augment took; enqueued on the current stream, no random draw, no host synchronisation."""
+        _augment took (after the elastic map, when the item has one: the weight map is computed from the warped
+        ids); enqueued on the current stream, no random draw, no host synchronisation."""
         c = self.weight_map
         inst = ops.rasterize_polygons(polys, list(range(1, len(polys) + 1)), h, w, device)
-        if flips[0]:
-            inst = ops.flip_mask(inst, 1)
-        if flips[1]:
-            inst = ops.flip_mask(inst, 0)
+        if grid is not None:
+            inst = ops.warp_labels(inst, grid, border=self.elastic["border"], flip_h=flips[0], flip_v=flips[1])
+        else:
+            if flips[0]:
+                inst = ops.flip_mask(inst, 1)
+            if flips[1]:
+                inst = ops.flip_mask(inst, 0)
         if c["separate"]:
             inst, mask = ops.separate_instances(inst, mask)
         wmap = ops.border_weight_map(inst, mask, class_weight=c["class_weight"], w0=c["w0"], sigma=c["sigma"],
@@ -268,17 +349,27 @@ class CellDataset:
         mask = ops.rasterize_polygons(polys, [l + 1 for l in labels], h, w, img.device)
         if self.cell_preprocess:
             img = self._apply_cell_specific_preprocessing(img.contiguous(), polys, labels)
-        flips = (False, False)
+        flips, grid = (False, False), None
         if self.split == "train":
+            if self.elastic is not None:  # geometric first, photometric second
+                grid = self._elastic_draw(h, w, img.device)
+                if grid is not None:
+                    img, mask = self._warp(img.contiguous(), mask, grid)
             img, mask, flips = self._augment(img.contiguous(), mask)
-        instance_masks = list(ops.rasterize_instances(polys, h, w, img.device, flip_h=flips[0], flip_v=flips[1]))
+        if grid is None:
+            instance_masks = list(ops.rasterize_instances(polys, h, w, img.device, flip_h=flips[0], flip_v=flips[1]))
+        else:  # rasterised unflipped, then through the item's map with the flips _augment took
+            instance_masks = list(ops.warp_labels(ops.rasterize_instances(polys, h, w, img.device), grid,
+                                                  border=self.elastic["border"], flip_h=flips[0], flip_v=flips[1]))
         tensor = self.transform(img) if self.transform else ops.to_tensor(img)
         # dataset.py:313-321; bboxes stay in the unflipped frame, as the reference leaves them
         item = {"image": tensor, "instance_masks": instance_masks, "instance_labels": labels, "bboxes": bboxes,
                 "semantic_mask": mask, "image_id": name, "original_size": original_size}
         if self.weight_map is not None:
             item["semantic_mask"], item["weight_map"], item["instance_label_map"] = self._weight_map_item(
-                polys, h, w, flips, mask, img.device)
+                polys, h, w, flips, mask, img.device, grid)
+        if self.elastic is not None:
+            item["warp_grid"] = grid  # None: the p draw skipped the item (or the split is not train)
         return item
 
 

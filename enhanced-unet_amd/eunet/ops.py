@@ -1247,6 +1247,97 @@ def flip_mask(mask, mode: int):
     return out
 
 
+# ---- elastic deformation and affine warp (warp.hip; U-Net paper §3.1, no reference counterpart) ----
+WARP_BORDERS = {"constant": 0, "reflect": 1}  # EUNET_WARP_CONSTANT, EUNET_WARP_REFLECT101
+WARP_GRID_MAX = 16
+
+
+def _warp_border(what, border):
+    if border not in WARP_BORDERS:
+        raise ValueError(f"{what}: unknown border {border!r}; known: {sorted(WARP_BORDERS)}")
+    return WARP_BORDERS[border]
+
+
+def _warp_map(what, grid):
+    if grid.dim() != 3 or grid.shape[2] != 2 or grid.dtype != torch.float32 or min(grid.shape[:2]) < 1:
+        raise ValueError(f"{what}: grid must be float32 [h, w, 2], got {grid.dtype} {tuple(grid.shape)}")
+    return grid.contiguous()
+
+
+def elastic_grid(h, w, ctrl, matrix=None, device="cuda"):
+    """eunet_warp_grid: the dense sampling map float32 [h, w, 2], (sx, sy) in absolute source pixels, of the 2x3
+    inverse (destination -> source) affine map `matrix` (host array; None: the identity) plus the bicubic
+    interpolation (F.interpolate, align_corners=True) of the control displacements ctrl [2, gh, gw] (host array
+    or device tensor; plane 0 dx, plane 1 dy, in pixels; 2 <= gh, gw <= 16)."""
+    import numpy as np
+    if isinstance(ctrl, torch.Tensor):
+        c = ctrl
+    else:
+        a = np.asarray(ctrl, dtype=np.float32)
+        if not np.isfinite(a).all():
+            raise ValueError("elastic_grid: ctrl holds non-finite values")
+        c = a
+    if len(c.shape) != 3 or c.shape[0] != 2:
+        raise ValueError(f"elastic_grid: ctrl must be [2, gh, gw], got {tuple(c.shape)}")
+    gh, gw = int(c.shape[1]), int(c.shape[2])
+    if not (2 <= gh <= WARP_GRID_MAX and 2 <= gw <= WARP_GRID_MAX):
+        raise ValueError(f"elastic_grid: control grid {gh} x {gw} outside 2..{WARP_GRID_MAX}")
+    if int(h) < 1 or int(w) < 1:
+        raise ValueError(f"elastic_grid: size {h} x {w} must be at least 1 x 1")
+    m = None
+    if matrix is not None:
+        mh = np.asarray(matrix, dtype=np.float64)
+        if mh.shape != (2, 3) or not np.isfinite(mh).all():
+            raise ValueError("elastic_grid: matrix must be a finite host 2x3 array")
+        m = ctypes.byref((ctypes.c_double * 6)(*mh.reshape(-1).tolist()))
+    if isinstance(c, torch.Tensor):
+        c = c.to(device=device, dtype=torch.float32).contiguous()
+    else:
+        c = upload(c, device)
+    out = torch.empty(int(h), int(w), 2, dtype=torch.float32, device=c.device)
+    call("eunet_warp_grid", _ptr(c), gh, gw, m, int(h), int(w), _ptr(out), _stream())
+    return out
+
+
+def warp_u8(img, grid, border="reflect", fill=0):
+    """eunet_warp_u8: HWC uint8 image (1..4 channels) gathered bilinearly through a map [ho, wo, 2] (elastic_grid's,
+    or any float32 map of absolute source coordinates) -> uint8 [ho, wo, c]; integer arithmetic in 1/32 pixel."""
+    b = _warp_border("warp_u8", border)
+    g = _warp_map("warp_u8", grid)
+    if img.dim() != 3 or img.dtype != torch.uint8 or not 1 <= img.shape[2] <= 4 or img.device != g.device:
+        raise ValueError(f"warp_u8: img must be uint8 [h, w, 1..4] on the map's device, got {img.dtype} {tuple(img.shape)}")
+    if not 0 <= int(fill) <= 255:
+        raise ValueError(f"warp_u8: fill {fill} outside 0..255")
+    hi, wi, c = img.shape
+    ho, wo = g.shape[:2]
+    out = torch.empty(ho, wo, c, dtype=torch.uint8, device=img.device)
+    call("eunet_warp_u8", _ptr(img.contiguous()), hi, wi, c, _ptr(g), ho, wo, b, int(fill), _ptr(out), _stream())
+    return out
+
+
+def warp_labels(x, grid, border="reflect", fill=0, flip_h: bool = False, flip_v: bool = False):
+    """eunet_warp_labels: an int64 [h, w] label map or a uint8 [n, h, w] stack gathered nearest-neighbour through
+    the map -> [ho, wo] / [n, ho, wo]; every output value is a source value or `fill`.  flip_h / flip_v mirror
+    the result (the training flips, as rasterize_instances takes them)."""
+    b = _warp_border("warp_labels", border)
+    g = _warp_map("warp_labels", grid)
+    ho, wo = g.shape[:2]
+    if x.dtype == torch.int64 and x.dim() == 2:
+        planes, (hi, wi), eb, shape = 1, x.shape, 8, (ho, wo)
+    elif x.dtype == torch.uint8 and x.dim() == 3:
+        planes, (hi, wi), eb, shape = x.shape[0], x.shape[1:], 1, (x.shape[0], ho, wo)
+        if not 0 <= int(fill) <= 255:
+            raise ValueError(f"warp_labels: fill {fill} outside 0..255 for a uint8 stack")
+    else:
+        raise ValueError(f"warp_labels: needs an int64 [h, w] map or a uint8 [n, h, w] stack, got {x.dtype} {tuple(x.shape)}")
+    if x.device != g.device:
+        raise ValueError("warp_labels: labels and map must be on one device")
+    out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    call("eunet_warp_labels", _ptr(x.contiguous()) if planes else None, eb, planes, hi, wi, _ptr(g), ho, wo, b, int(fill),
+         int(bool(flip_h)), int(bool(flip_v)), _ptr(out) if planes else None, _stream())
+    return out
+
+
 def augment_u8(img, alpha=None, beta=None, noise=None, lut=None):
     """In-place on a contiguous uint8 device tensor (reference order: alpha, beta, noise, LUT)."""
     flags = (1 if alpha is not None else 0) | (2 if beta is not None else 0) | \

@@ -389,6 +389,44 @@ int eunet_bce_dice_bwd_w(const float* logits, const int64_t* target, const float
                          int h, int w, const eunet_bce_dice_params* params, const float* sums,
                          const float* gloss, float* glogits, void* stream);
 
+/* ---- elastic deformation and affine warp of image and labels (warp.hip) -------------------------
+ * No reference line to cite: the reference's augmentations are photometric or a mirror.  The deformation is
+ * the one of Ronneberger et al., "U-Net" (2015), §3.1: random displacement vectors on a coarse grid, a
+ * per-pixel displacement by bicubic interpolation, image and labels moved together; this comment is the
+ * definition.  No host synchronisation, no allocation; enqueued on stream only.
+ *
+ * eunet_warp_grid writes the dense sampling map grid [h][w][2] fp32, (sx, sy) in absolute source pixels:
+ *   sx = m00 x + m01 y + m02 + Dx(y, x)      sy = m10 x + m11 y + m12 + Dy(y, x)
+ * m: six host doubles (nullable = identity), the 2x3 inverse map, destination to source, as cv2.warpAffine
+ * with WARP_INVERSE_MAP; used in fp32.  D is the bicubic interpolation of the control displacements ctrl
+ * [2][gh][gw] (device fp32; plane 0 dx, plane 1 dy, in pixels), defined to be exactly
+ * F.interpolate(ctrl[None], size=(h, w), mode="bicubic", align_corners=True): the cubic-convolution kernel
+ * with A = -0.75 at u = x (gw - 1) / (w - 1) (0 when w == 1), taps floor(u) - 1 .. floor(u) + 2 with indices
+ * clamped to [0, gw - 1]; the same along y.  2 <= gh, gw <= 16; 1 <= h, w <= 2^20. */
+int eunet_warp_grid(const float* ctrl, int gh, int gw, const double* m, int h, int w, float* grid, void* stream);
+/* Both gathers read a map grid [ho][wo][2] (8-byte aligned) whose size is independent of the source's
+ * (hi, wi), and are pure functions of its fp32 values: with sx clamped to +-2^20,
+ *   qx = rint(32 sx)  (round-half-even; the product is exact in fp32), qy likewise;
+ * a non-finite sx or sy gives `fill` under both border rules.  Every tap index goes through the border rule
+ * on its own:
+ *   EUNET_WARP_CONSTANT:   an index outside [0, n) contributes `fill`
+ *   EUNET_WARP_REFLECT101: r = i mod 2(n - 1) taken non-negative, r = 2(n - 1) - r if r >= n; r = 0 if n == 1
+ *                          (any number of reflections)
+ * eunet_warp_u8: bilinear, HWC uint8, 1 <= c <= 4, integer after the one rounding above:
+ *   ix = qx >> 5 (floor), fx = qx & 31, iy and fy likewise; taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1)
+ *   with weights (32-fx)(32-fy), fx(32-fy), (32-fx)fy, fx fy;  out = (sum w p + 512) >> 10.
+ * eunet_warp_labels: nearest, ix = (qx + 16) >> 5 and iy likewise, over `planes` planes [planes][hi][wi] ->
+ *   [planes][ho][wo] of elem_bytes = 8 (int64) or 1 (uint8; fill in 0..255) that share the one map; output
+ *   pixel (y, x) reads grid[flip_v ? ho-1-y : y][flip_h ? wo-1-x : x], so the flagged result is the unflagged
+ *   one mirrored (as eunet_rasterize_instances takes the training flips).  planes == 0 is a no-op.
+ * Not in place.  Sides up to 2^20; a source (plane) below 2^31 bytes (pixels). */
+#define EUNET_WARP_CONSTANT 0
+#define EUNET_WARP_REFLECT101 1
+int eunet_warp_u8(const uint8_t* src, int hi, int wi, int c, const float* grid, int ho, int wo, int border,
+                  int fill, uint8_t* dst, void* stream);
+int eunet_warp_labels(const void* src, int elem_bytes, int planes, int hi, int wi, const float* grid, int ho,
+                      int wo, int border, long long fill, int flip_h, int flip_v, void* dst, void* stream);
+
 /* ---- backward helpers ----------------------------------------------------
  * BN(+ReLU) backward (autograd of models.py:220-224): g is the gradient w.r.t.
  * the ReLU output, y the pre-BN conv output, mean / invstd the batch statistics and
@@ -419,7 +457,7 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
  * eunet_debug_enabled: 1 in the debug build, 0 in the release library (where the checks compile away).
  * eunet_debug_status: synchronises the device; *count = failed checks since the last reset,
  * *unit_line = unit * 100000 + source line of the first (units: 1 capi, 2 conv3x3, 3 bn_pool_up,
- * 4 head, 5 instances, 6 baselines, 7 upconv, 8 bce_dice, 9 weightmap, 10 tiling; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
+ * 4 head, 5 instances, 6 baselines, 7 upconv, 8 bce_dice, 9 weightmap, 10 tiling, 11 warp; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
 int eunet_debug_enabled(void);
 int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset);
 int eunet_debug_selftest(void* stream);
