@@ -144,6 +144,7 @@ SIGNATURES = {
     "eunet_probs_to_mask": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
     "eunet_sigmoid_crop": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_probs_threshold": [_f, c_int, c_int, c_int, c_float, _f, c_void_p],
+    "eunet_score_hist": [_f, _f, c_int, c_int, c_int64, _f, c_int, c_int, _f, _f, c_void_p],
     "eunet_tile_gather": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_tile_blend": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, _f, c_int,
                          c_int, c_int, _f, c_void_p],

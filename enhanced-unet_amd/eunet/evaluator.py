@@ -11,6 +11,9 @@
     .evaluate(dataloader, coco_map=False) -> mean semantic / instance / viability rows   # train_eval.py:852-1021
         (coco_map=True adds bbox_mAP / segm_mAP, train_eval.py:951-992, 1007-1011)
     .evaluate_semantic(dataloader) -> mean semantic metrics     # train_eval.py:852-904 (semantic rows)
+    .evaluate_curves(dataloader) -> per-class ROC / PR / calibration statistics over all pixels
+        (what visualization.py:1096-1199, 1819-1900 plot)
+    .evaluate_with_curves(dataloader, coco_map=False) -> evaluate()'s rows plus auc_ / ap_ / ece_<class>
 
 Every per-pixel step runs in HIP (evalpath.hip): the flips and 0.75/1.25
 rescales (PyTorch bilinear index math), softmax + crop, the TTA mean, the
@@ -42,6 +45,15 @@ eunet_coco_match); only the match tables come back, and
 metrics.coco_map_from_matches accumulates them once at the end.  The default
 evaluate() returns the 23 EVALUATE_KEYS rows as before.
 
+Pixel-level ROC, PR and calibration statistics stay on the device as well: the reference copies every
+image's softmax to the host, extends Python lists pixel by pixel and sorts them with sklearn, for 20 images
+at most (train_eval.py:1291-1319).  Here each image's probabilities are binned once into an exact integer
+histogram (ops.score_hist, curves.hip) that accumulates over the whole loader; one copy comes back and
+metrics.curve_metrics_from_hist forms the curves, the AUC with a hard bound on its binning error, the
+average precision, the reliability curve and its ECE.  Two deliberate departures from the reference's
+plots: the last calibration bin holds p == 1, and ignored pixels (255) are left out of the calibration
+too, as they are out of its ROC and PR curves.
+
 Overlap-tile inference (no reference counterpart: the reference resizes every image down to max_size):
 Evaluator(..., tile=T) sends an image whose padded size exceeds T in either axis through the network tile by
 tile (eunet.tiling.plan; ops.tile_gather, forward_lowres on tile_batch tiles at a time, one ops.tile_blend
@@ -60,8 +72,9 @@ import torch
 import torch.nn.functional as F
 
 from . import ops, tiling
-from .metrics import (calculate_dice, calculate_instance_metrics, calculate_iou, calculate_semantic_metrics,
-                      calculate_viability_metrics, coco_image_matches, coco_map_from_matches)
+from .metrics import (CLASS_NAMES, _dev_long, calculate_dice, calculate_instance_metrics, calculate_iou,
+                      calculate_semantic_metrics, calculate_viability_metrics, coco_image_matches,
+                      coco_map_from_matches, curve_edges, curve_metrics_from_hist)
 
 TTA_SCALES = (0.75, 1.25)
 
@@ -79,6 +92,15 @@ EVALUATE_KEYS = ("sem_mean_iou", "sem_mean_dice", "sem_background_iou", "sem_bac
                  "gt_dead_count")
 # the two rows evaluate(coco_map=True) adds (train_eval.py:871-872, 1007-1011)
 COCO_KEYS = ("bbox_mAP", "segm_mAP")
+CURVE_STATS = ("auc", "ap", "ece")
+
+
+def curve_keys(class_names) -> tuple:
+    return tuple(f"{s}_{name}" for name in class_names for s in CURVE_STATS)
+
+
+# the rows evaluate_with_curves() adds for a three-class model (visualization.py:1131, 1184; the ECE of :1847-1864)
+CURVE_KEYS = curve_keys(CLASS_NAMES)
 
 
 def _perimeter(n_axis: int, n_diag: int) -> float:
@@ -263,6 +285,46 @@ class Evaluator:
                 dices.append(calculate_dice(pred == 1, gt > 0))
         return {"bin_iou": float(np.mean(ious)) if ious else 0.0, "bin_dice": float(np.mean(dices)) if dices else 0.0}
 
+    # ---- visualization.py:1096-1199, 1819-1900 without the host round trip ---------
+    def _bin_scores(self, probs: torch.Tensor, semantic_mask, edges, acc):
+        """One image's probabilities [K,h,w] and ground truth into the running (hist, invalid) pair."""
+        gt = _dev_long(semantic_mask, probs.device).contiguous()
+        return ops.score_hist(probs.contiguous(), gt, edges, out=acc)
+
+    def _curve_result(self, acc, edges, n_cal: int, n_conf: int) -> Dict:
+        hist, invalid = acc
+        flat = torch.cat([hist.reshape(-1), invalid]).cpu().numpy()  # the one copy to the host
+        hist_h = flat[:-1].reshape(tuple(hist.shape))
+        result = curve_metrics_from_hist(hist_h, edges, n_cal=n_cal, n_conf=n_conf)
+        result.update(invalid=int(flat[-1]), hist=hist_h, edges=edges)
+        return result
+
+    def evaluate_curves(self, dataloader, edges=None, tta: bool = True, n_cal: int = 10, n_conf: int = 50) -> Dict:
+        """Per-class ROC, PR and calibration statistics over every pixel of the loader:
+        metrics.curve_metrics_from_hist's dict ({class name: {fpr, tpr, thresholds, auc, precision, recall,
+        ap, auc_resolution, cal_acc, cal_conf, cal_count, ece, conf_hist, ...}}) plus "invalid" (pixels whose
+        probability was NaN, infinite or negative), "hist" (the int64 [K, B, 3] histogram) and "edges".
+
+        tta=True bins predict_probs, the probabilities predict_semantic_mask converts; tta=False one
+        _run_model_single view, the reference's own definition (train_eval.py:1301-1303), tiled where tile=
+        says so.  edges: None for metrics.curve_edges() or a table of its form.  Works for
+        activation="sigmoid" as well (one logit: the class "foreground", positive where the mask is >= 1)."""
+        edges = curve_edges() if edges is None else np.asarray(edges, dtype=np.float32)
+        acc = None
+        self.model.eval()
+        for batch in dataloader:
+            for i, item in enumerate(batch["batch_items"]):
+                if tta:
+                    probs = self.predict_probs(batch["images"][i])
+                else:
+                    with torch.no_grad():
+                        x = self._prepare_image_tensor(batch["images"][i])
+                        probs = self._run_model_single(x.contiguous().float())
+                acc = self._bin_scores(probs, item["semantic_mask"], edges, acc)
+        if acc is None:
+            raise ValueError("evaluate_curves: the loader holds no image")
+        return self._curve_result(acc, edges, n_cal, n_conf)
+
     # ---- train_eval.py:654-850 -------------------------------------------------
     def _split_large_region(self, region, area: int, final, next_label: int, min_area: int) -> int:
         """The erosion ladder of one region of >= 200 px (train_eval.py:697-785): writes the pieces into
@@ -375,10 +437,22 @@ class Evaluator:
         COCOeval stats[0] over all images, metrics.calculate_coco_metrics' value): per image the matching
         runs on the device and only scores, match tables and ground-truth counts are kept, accumulated once
         at the end.  Without the flag those keys are left out of the dict."""
+        return self._evaluate(dataloader, coco_map, False)
+
+    def evaluate_with_curves(self, dataloader, coco_map: bool = False) -> Dict[str, float]:
+        """evaluate()'s dict plus auc_<class>, ap_<class> and ece_<class> (CURVE_KEYS for three classes;
+        evaluate_curves' values with tta=True) from the same forward: the probabilities are predicted once,
+        binned and converted.  A method of its own because evaluate's signature is the reference's plus
+        coco_map and is pinned as such."""
+        return self._evaluate(dataloader, coco_map, True)
+
+    def _evaluate(self, dataloader, coco_map: bool, curves: bool) -> Dict[str, float]:
         acc: Dict[str, list] = {k: [] for k in EVALUATE_KEYS}
         coco_bbox, coco_segm = [], []
         n_pred = n_gt = 0  # over all images; ground-truth ids are the running positions (metrics.py:240-242)
         orphan = False  # predictions on an image without ground truth: COCO.loadRes refuses them
+        edges = curve_edges() if curves else None
+        hist = None
 
         def collect(metrics):
             for k, v in metrics.items():
@@ -388,7 +462,12 @@ class Evaluator:
         for batch in dataloader:
             for i, item in enumerate(batch["batch_items"]):
                 gt_masks, gt_labels = item["instance_masks"], item["instance_labels"]
-                pred = self.predict_semantic_mask(batch["images"][i])
+                if curves:  # predict_semantic_mask's two steps, with the probabilities binned in between
+                    probs = self.predict_probs(batch["images"][i])
+                    hist = self._bin_scores(probs, item["semantic_mask"], edges, hist)
+                    pred = self._convert_probs_to_mask(probs)
+                else:
+                    pred = self.predict_semantic_mask(batch["images"][i])
                 collect(calculate_semantic_metrics(pred, item["semantic_mask"]))
                 masks, labels, scores = self.semantic_to_instances(pred)
                 collect(calculate_instance_metrics(masks, labels, scores, gt_masks, gt_labels))
@@ -414,4 +493,7 @@ class Evaluator:
             elif n_pred and n_gt:
                 result["bbox_mAP"] = coco_map_from_matches(coco_bbox)
                 result["segm_mAP"] = coco_map_from_matches(coco_segm)
+        if curves and hist is not None:
+            for name, m in curve_metrics_from_hist(hist[0], edges).items():
+                result.update({f"{s}_{name}": m[s] for s in CURVE_STATS})
         return result

@@ -880,6 +880,107 @@ def probs_threshold(probs, threshold: float = 0.5):
     return mask
 
 
+# ---- pixel-level score histograms (curves.hip) ---------------------------------------------
+SCORE_HIST_MAX_BINS = 3072
+_edge_tables: dict = {}  # (device, table bytes) -> the validated table on that device
+_edge_checked: dict = {}  # (device, data_ptr, numel, version) of the device tables already validated
+
+
+@_dispatched("T T T i T! T!")
+def score_hist(probs, mask, edges, ignore_index, hist, invalid):
+    n, k = probs.shape[:2]
+    hw = probs[0, 0].numel()
+    # one read of the probabilities and, per class, of the mask
+    with kprof.timed("score_hist", 0.0, 4.0 * probs.numel() + 8.0 * k * mask.numel()):
+        call("eunet_score_hist", _ptr(probs), _ptr(mask), n, k, hw, _ptr(edges), edges.numel() - 1, ignore_index,
+             _ptr(hist), _ptr(invalid), _stream())
+
+
+_score_hist_op = score_hist  # torch.ops.eunet.score_hist adds into hist and invalid; the function below allocates them
+
+
+def _check_edges(e):
+    """e: a host float32 array.  The table eunet_score_hist requires, or ValueError."""
+    import numpy as np
+    if e.ndim != 1 or e.size < 2 or e.size - 1 > SCORE_HIST_MAX_BINS:
+        raise ValueError(f"score_hist: edges must be bins + 1 values, bins = 1..{SCORE_HIST_MAX_BINS}, "
+                         f"got shape {tuple(e.shape)}")
+    if e[0] != 0.0 or e[-1] != 1.0 or not bool(np.all(np.diff(e) > 0)):
+        raise ValueError("score_hist: edges must be strictly increasing from edges[0] = 0 to edges[bins] = 1")
+
+
+def score_edges(edges, device):
+    """The validated fp32 edge table on `device`: a host array (or sequence) is checked, uploaded once and kept;
+    a device tensor is checked once (one copy to the host) and passed through."""
+    import numpy as np
+    device = torch.device(device)
+    if isinstance(edges, torch.Tensor):
+        if edges.dtype != torch.float32 or edges.dim() != 1 or not edges.is_contiguous():
+            raise ValueError(f"score_hist: edges must be a contiguous 1-D fp32 table, got {tuple(edges.shape)} "
+                             f"{edges.dtype}")
+        if not edges.is_cuda:
+            return score_edges(edges.numpy(), device)
+        if edges.device != device:
+            raise ValueError(f"score_hist: edges live on {edges.device}, probs on {device}")
+        key = (str(device), edges.data_ptr(), edges.numel(), edges._version)
+        if key not in _edge_checked:
+            _check_edges(edges.cpu().numpy())
+            if len(_edge_checked) >= 16:
+                _edge_checked.clear()
+            _edge_checked[key] = True
+        return edges
+    e = np.ascontiguousarray(np.asarray(edges), dtype=np.float32)
+    _check_edges(e)
+    key = (str(device), e.tobytes())
+    if key not in _edge_tables:
+        if len(_edge_tables) >= 16:
+            _edge_tables.clear()
+        _edge_tables[key] = torch.from_numpy(e.copy()).to(device)
+    return _edge_tables[key]
+
+
+def score_hist(probs, mask, edges, ignore_index: int = 255, out=None):
+    """probs [K, h, w] or [N, K, h, w] fp32 (K = 1..3), mask int64 [h, w] or [N, h, w], edges bins + 1 floats
+    (metrics.curve_edges; a host array or a device tensor) -> (hist int64 [K, bins, 3], invalid int64 [1]).
+
+    hist[c, b] = (#negatives, #positives, sum of llrint(min(p, 1) 2^24)) of class c in score bin b
+    (edges[b] <= p < edges[b+1] in fp32, the last bin closed); a pixel of mask == ignore_index counts nowhere,
+    a p that is NaN, +-inf or < 0 only in invalid (include/eunet.h, eunet_score_hist).  out = (hist, invalid)
+    is added to -- how a validation set streams through; None allocates zeroed ones."""
+    if not isinstance(probs, torch.Tensor) or not isinstance(mask, torch.Tensor):
+        raise ValueError("score_hist: probs and mask must be tensors")
+    if not probs.is_cuda or not mask.is_cuda or probs.device != mask.device:
+        raise ValueError(f"score_hist: probs and mask must live on one GPU, got {probs.device} and {mask.device}")
+    if probs.dtype != torch.float32 or mask.dtype != torch.int64:
+        raise ValueError(f"score_hist: probs must be fp32 and mask int64, got {probs.dtype} and {mask.dtype}")
+    if probs.dim() == 3 and mask.dim() == 2:
+        probs, mask = probs.unsqueeze(0), mask.unsqueeze(0)
+    elif probs.dim() != 4 or mask.dim() != 3:
+        raise ValueError(f"score_hist: probs [K, h, w] with mask [h, w], or [N, K, h, w] with [N, h, w]; got "
+                         f"{tuple(probs.shape)} and {tuple(mask.shape)}")
+    n, k, h, w = probs.shape
+    if tuple(mask.shape) != (n, h, w) or not 1 <= k <= 3 or n < 1 or h * w < 1:
+        raise ValueError(f"score_hist: probs {tuple(probs.shape)} (K = 1..3, no empty axis) and mask "
+                         f"{tuple(mask.shape)} do not agree")
+    if not probs.is_contiguous() or not mask.is_contiguous():
+        raise ValueError("score_hist: probs and mask must be contiguous")
+    if not -2 ** 31 <= int(ignore_index) < 2 ** 31:
+        raise ValueError(f"score_hist: ignore_index {ignore_index} is not an int32")
+    e = score_edges(edges, probs.device)
+    bins = e.numel() - 1
+    if out is None:
+        hist = torch.zeros(k, bins, 3, dtype=torch.int64, device=probs.device)
+        invalid = torch.zeros(1, dtype=torch.int64, device=probs.device)
+    else:
+        hist, invalid = out
+        for name, t, shape in (("hist", hist, (k, bins, 3)), ("invalid", invalid, (1,))):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.int64 or \
+                    not t.is_contiguous() or t.device != probs.device:
+                raise ValueError(f"score_hist: out {name} must be a contiguous int64 {shape} on {probs.device}")
+    _score_hist_op(probs, mask, e, int(ignore_index), hist, invalid)
+    return hist, invalid
+
+
 # ---- overlap-tile inference (tiling.hip; the geometry is eunet.tiling.TilePlan) ----------
 TILE_ACTIVATIONS = {"none": 0, "softmax": 1, "sigmoid": 2}  # EUNET_TILE_ACT_*
 

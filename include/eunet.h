@@ -570,6 +570,32 @@ int eunet_sigmoid_crop(const float* logits, int k, int hp, int wp, int h, int w,
 int eunet_probs_threshold(const float* probs, int k, int h, int w, float threshold, int64_t* mask,
                           void* stream);
 
+/* ---- pixel-level score histograms (curves.hip) --------------------------------
+ * The one device pass behind the ROC, PR and calibration statistics of visualization.py:1096-1199, 1819-1900
+ * (plot_roc_curves, plot_pr_curves, plot_calibration_curve), which the reference feeds by copying every
+ * image's softmax to the host (train_eval.py:1291-1306).  probs fp32 [n][k][hw] (k = 1..3), mask int64
+ * [n][hw]; edges: bins + 1 device floats (bins = 1..3072), strictly increasing with edges[0] = 0 and
+ * edges[bins] = 1 (the caller's duty: only pointers and ranges are checked here).
+ *   hist int64 [k][bins][3] = per class c and bin b (#negatives, #positives, confidence sum); invalid int64 [1].
+ * Both are ADDED to, never zeroed: a validation set accumulates into one pair (integer adds, order-free).
+ * Bin: bin(p) = the i with edges[i] <= p < edges[i+1], compared in fp32, and the last bin is closed: every
+ *   finite p >= edges[bins-1] goes to bin bins-1 (p == 1, and a test-time-augmentation mean that rounds a hair
+ *   above 1).  This is a deliberate difference from the reference's `p >= e[i] & p < e[i+1]`
+ *   (visualization.py:1854), which silently drops every saturated p == 1.0; it is the convention of sklearn's
+ *   calibration_curve.  -0.0 goes to bin 0.  A p that is NaN, +-inf or < 0 adds 1 to invalid[0] and counts
+ *   nowhere else.
+ * Truth: a pixel with mask == ignore_index counts nowhere, for any class, and its p is not examined (the
+ *   reference filters 255 in its ROC and PR functions but not in its calibration function; here the rule is the
+ *   same for all three).  Otherwise the pixel is a positive of class c when mask == c; for k == 1 when
+ *   mask >= 1 (the one-logit target of eunet_bce_dice_fwd).  A label outside [0, k) is a negative of every
+ *   class, as in the reference.
+ * Conf: hist[c][b][2] += llrint(min(p, 1) * 2^24): the scaling is exact in fp32 and the rounding is to nearest
+ *   even, so the sum is an integer and a pure function of the input; a bin's mean confidence is
+ *   conf / 2^24 / (neg + pos), within 2^-25 of the true mean. */
+int eunet_score_hist(const float* probs, const int64_t* mask, int n, int k, long long hw,
+                     const float* edges, int bins, int ignore_index, int64_t* hist, int64_t* invalid,
+                     void* stream);
+
 /* ---- overlap-tile inference (tiling.hip) -------------------------------------
  * Prediction on an image larger than one forward pass (no reference line: the reference's only answer to a
  * large field of view is the resize down to max_size, dataset.py; overlap-tile prediction is the strategy
