@@ -48,6 +48,10 @@ class BCEDiceParams(ctypes.Structure):
 BCE_TARGET_AUTO, BCE_TARGET_ONEHOT, BCE_TARGET_FOREGROUND = 0, 1, 2  # EUNET_BCE_TARGET_*
 WMAP_RADIUS_AUTO = -1  # EUNET_WMAP_RADIUS_AUTO
 WMAP_MAX_RADIUS = 48
+EDT_EQ, EDT_NE, EDT_EDGE = 0, 1, 2  # EUNET_EDT_*
+EDT_NONE = 2 ** 31 - 1
+EDT_MAX_VALUES, EDT_MAX_SIDE = 8, 8192
+BOUNDARY_MAX_CAP, BOUNDARY_MAX_RADII = 64, 8
 
 
 class OptTensor(ctypes.Structure):
@@ -145,6 +149,10 @@ SIGNATURES = {
     "eunet_sigmoid_crop": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_probs_threshold": [_f, c_int, c_int, c_int, c_float, _f, c_void_p],
     "eunet_score_hist": [_f, _f, c_int, c_int, c_int64, _f, c_int, c_int, _f, _f, c_void_p],
+    "eunet_edt_sq": [_f, c_int, c_int, c_int, POINTER(c_int64), c_int, c_int, _f, c_void_p],
+    "eunet_boundary_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],
+    "eunet_boundary_stats": [_f, _f, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, _f, _f, _f, _f,
+                             c_void_p],
     "eunet_tile_gather": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_tile_blend": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, _f, c_int,
                          c_int, c_int, _f, c_void_p],

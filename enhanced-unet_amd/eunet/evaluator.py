@@ -14,6 +14,8 @@
     .evaluate_curves(dataloader) -> per-class ROC / PR / calibration statistics over all pixels
         (what visualization.py:1096-1199, 1819-1900 plot)
     .evaluate_with_curves(dataloader, coco_map=False) -> evaluate()'s rows plus auc_ / ap_ / ece_<class>
+    .evaluate_boundary(dataloader) -> per-class contour metrics (HD, HD95, ASSD, surface Dice, boundary F1,
+        Boundary IoU) and the two lists of visualization.py:1687-1751 (plot_boundary_accuracy)
 
 Every per-pixel step runs in HIP (evalpath.hip): the flips and 0.75/1.25
 rescales (PyTorch bilinear index math), softmax + crop, the TTA mean, the
@@ -54,6 +56,13 @@ average precision, the reliability curve and its ECE.  Two deliberate departures
 plots: the last calibration bin holds p == 1, and ignored pixels (255) are left out of the calibration
 too, as they are out of its ROC and PR curves.
 
+Contour quality (evaluate_boundary): the reference's plot_boundary_accuracy copies every mask to the host and
+runs scipy.ndimage morphology per image and class.  Here the predicted mask never leaves the device: an exact
+Euclidean distance transform of both maps' class edges (ops.distance_transform_sq's kernels) feeds one integer
+statistics pass (ops.boundary_stats, boundary.hip) that accumulates over the loader; one copy comes back and
+metrics.boundary_metrics_from_stats forms the Hausdorff distance, HD95, the average symmetric surface distance,
+surface Dice, boundary F1 and Boundary IoU, and the reference's boundary / interior IoU lists.
+
 Overlap-tile inference (no reference counterpart: the reference resizes every image down to max_size):
 Evaluator(..., tile=T) sends an image whose padded size exceeds T in either axis through the network tile by
 tile (eunet.tiling.plan; ops.tile_gather, forward_lowres on tile_batch tiles at a time, one ops.tile_blend
@@ -72,9 +81,10 @@ import torch
 import torch.nn.functional as F
 
 from . import ops, tiling
-from .metrics import (CLASS_NAMES, _dev_long, calculate_dice, calculate_instance_metrics, calculate_iou,
-                      calculate_semantic_metrics, calculate_viability_metrics, coco_image_matches,
-                      coco_map_from_matches, curve_edges, curve_metrics_from_hist)
+from .metrics import (CLASS_NAMES, _dev_long, boundary_metrics_from_stats, calculate_boundary_stats, calculate_dice,
+                      calculate_instance_metrics, calculate_iou, calculate_semantic_metrics,
+                      calculate_viability_metrics, coco_image_matches, coco_map_from_matches, curve_edges,
+                      curve_metrics_from_hist)
 
 TTA_SCALES = (0.75, 1.25)
 
@@ -324,6 +334,49 @@ class Evaluator:
         if acc is None:
             raise ValueError("evaluate_curves: the loader holds no image")
         return self._curve_result(acc, edges, n_cal, n_conf)
+
+    # ---- visualization.py:1687-1751 and the contour metrics, without the host round trip ---------
+    def _predict_mask_device(self, image: torch.Tensor) -> torch.Tensor:
+        """predict_semantic_mask's int64 mask [h, w], left on the device."""
+        probs = self.predict_probs(image).to(self.device)
+        if self.activation == "sigmoid":
+            return ops.probs_threshold(probs, self.threshold)
+        return ops.probs_to_mask(probs)
+
+    def evaluate_boundary(self, dataloader, tolerances=(1, 2, 3), band_radii=(2,), cap: int = 64,
+                          ignore_index: int = 255) -> Dict:
+        """Contour metrics over the loader: metrics.boundary_metrics_from_stats' dict ({class name: {nsd,
+        boundary_precision, boundary_recall, boundary_f1, hd, hd95, hd95_exceeds_cap, assd, boundary_iou, ...}},
+        pooled over the edge pixels of all images, plus the reference's per-image boundary_ious_ref /
+        interior_ious_ref lists and their means) and the raw integer buffers "surf", "band" and "refrows" (numpy)
+        with "cap" and "band_radii".
+
+        Each image's mask is predicted as predict_semantic_mask predicts it and stays on the device; the
+        statistics accumulate there and come back in one copy.  A one-logit sigmoid model is scored on the
+        classes background / foreground against the ground truth binarised as evaluate_binary does (gt >= 1,
+        ignore_index kept)."""
+        one_logit = self.activation == "sigmoid" and getattr(self.model, "num_classes", None) == 1
+        names = ("background", "foreground") if one_logit else CLASS_NAMES
+        acc = None
+        for batch in dataloader:
+            for i, item in enumerate(batch["batch_items"]):
+                pred = self._predict_mask_device(batch["images"][i])
+                gt = _dev_long(item["semantic_mask"], pred.device)
+                if one_logit:
+                    gt = torch.where(gt == ignore_index, gt, (gt >= 1).long())
+                acc = calculate_boundary_stats(pred, gt, num_classes=len(names), ignore_index=ignore_index, cap=cap,
+                                               band_radii=band_radii, out=acc)
+        if acc is None:
+            raise ValueError("evaluate_boundary: the loader holds no image")
+        parts = [acc["surf"].reshape(-1), acc["band"].reshape(-1), acc["refrows"].reshape(-1)]
+        flat = torch.cat(parts).cpu().numpy()  # the one copy to the host
+        cuts = np.cumsum([p.numel() for p in parts])
+        host = dict(acc, surf=flat[:cuts[0]].reshape(tuple(acc["surf"].shape)),
+                    band=flat[cuts[0]:cuts[1]].reshape(tuple(acc["band"].shape)),
+                    refrows=flat[cuts[1]:].reshape(tuple(acc["refrows"].shape)))
+        result = boundary_metrics_from_stats(host, tolerances=tolerances, class_names=names)
+        result.update(host)
+        return result
 
     # ---- train_eval.py:654-850 -------------------------------------------------
     def _split_large_region(self, region, area: int, final, next_label: int, min_area: int) -> int:

@@ -33,6 +33,13 @@ iscrowd and RLE decoding are not built.
 The pixel-level ROC / PR / calibration statistics that visualization.py:1096-1199,
 1819-1900 plot, from the integer score histogram of ops.score_hist (curves.hip):
 numpy only, no sklearn.
+
+    calculate_boundary_stats(pred, gt, num_classes=3, ignore_index=255, cap=64, band_radii=(2,), out=None)
+    boundary_metrics_from_stats(stats, tolerances=(1, 2, 3), class_names=None) -> {class: {...}, ...}
+
+The contour metrics (Hausdorff distance, HD95, average symmetric surface distance, surface Dice, boundary F1,
+Boundary IoU) and the two lists of visualization.py:1687-1751 (plot_boundary_accuracy), from the integer
+statistics of ops.boundary_stats (boundary.hip), which rest on an exact distance transform on the device.
 """
 from __future__ import annotations
 
@@ -507,6 +514,156 @@ def curve_metrics_from_hist(hist, edges, class_names: Optional[Sequence[str]] = 
 
 
 # ---- viability (metrics.py:304-340) -----------------------------------------------------------------
+# ---- contour metrics from the boundary statistics (visualization.py:1687-1751 and the field's metrics) ----
+DIST_SCALE = float(2 ** 16)  # the fixed point of the statistics' distance sums (eunet_boundary_stats)
+
+
+def calculate_boundary_stats(pred, gt, num_classes: int = 3, ignore_index: int = 255, cap: int = 64,
+                             band_radii: Sequence[int] = (2,), out: Optional[Dict] = None) -> Dict:
+    """The integer boundary statistics of one mask pair [h, w] or of a batch [n, h, w] (numpy arrays, copied to
+    the device, or tensors), as device buffers:
+      {"surf": int64 [k, 2, cap^2 + 5], "band": int64 [k, nr, 3], "refrows": int64 [images, k, 2, 3],
+       "cap", "band_radii", "ignore_index"}   (ops.boundary_stats; include/eunet.h, eunet_boundary_stats).
+    out: the dict of an earlier call with the same num_classes, ignore_index, cap and band_radii; surf and band
+    are added to in place (the maximum combined by max) and the new images' refrows are appended -- how a
+    validation set accumulates.  The same dict is returned."""
+    p = _dev_long(pred).contiguous()
+    g = _dev_long(gt, p.device).contiguous()
+    if p.shape != g.shape:
+        raise ValueError(f"mask shapes differ: {tuple(p.shape)} vs {tuple(g.shape)}")
+    radii = tuple(int(r) for r in band_radii)
+    if out is None:
+        surf, band, refrows = ops.boundary_stats(p, g, num_classes, ignore_index, cap, radii)
+        return {"surf": surf, "band": band, "refrows": refrows, "cap": int(cap), "band_radii": radii,
+                "ignore_index": int(ignore_index)}
+    if tuple(out["surf"].shape) != (int(num_classes), 2, int(cap) ** 2 + 5) or out["cap"] != int(cap) or \
+            tuple(out["band_radii"]) != radii or out["ignore_index"] != int(ignore_index):
+        raise ValueError("calculate_boundary_stats: out was made with another num_classes, ignore_index, cap or "
+                         "band_radii")
+    n = 1 if p.dim() == 2 else p.shape[0]
+    rows = torch.zeros(n, int(num_classes), 2, 3, dtype=torch.int64, device=p.device)
+    ops.boundary_stats(p, g, num_classes, ignore_index, cap, radii, out=(out["surf"], out["band"], rows))
+    out["refrows"] = torch.cat([out["refrows"], rows])
+    return out
+
+
+def _host(a) -> np.ndarray:
+    return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _ratio(a, b) -> float:
+    return float(a) / float(b) if b else float("nan")
+
+
+def _percentile_rank(n: int, q: float) -> int:
+    """The 1-based rank of the nearest-rank q-quantile of n values: numpy's method="inverted_cdf"."""
+    return min(max(int(np.ceil(n * q)), 1), n)
+
+
+def boundary_metrics_from_stats(stats: Dict, tolerances: Sequence[int] = (1, 2, 3),
+                                class_names: Optional[Sequence[str]] = None) -> Dict:
+    """The contour metrics per class from calculate_boundary_stats' buffers (pure numpy; one copy to the host
+    when they are device tensors).  Distances are in pixels, between the edges E_c of the two maps (the class's
+    pixels with a 4-neighbour outside the class or the image: MONAI's get_mask_edges).
+
+    Everything except the two reference rows is POOLED over the edge pixels of all accumulated images, not a
+    mean of per-image values.  Returns {class name: {...}, "boundary_ious_ref", "interior_ious_ref",
+    "boundary_iou_ref", "interior_iou_ref"} (default names CLASS_NAMES[:k]) with, per class,
+      n_pred_edge, n_gt_edge
+      nsd[t]                 surface Dice at tolerance t: (#pred edges within t of a gt edge + #gt edges within t
+                             of a pred edge) / (n_pred_edge + n_gt_edge); t an integer <= cap
+      boundary_precision[t], boundary_recall[t], boundary_f1[t]   the two fractions on their own, and their
+                             harmonic mean (0 when both are 0)
+      hd                     the Hausdorff distance: sqrt of the larger directional maximum; inf when, in some
+                             image, one map has an edge of the class and the other none; nan without any edge
+      hd95, hd95_exceeds_cap the larger of the two directions' nearest-rank 95th percentiles (the smallest
+                             distance with at least 95 % of that direction's edge pixels at or below it, numpy's
+                             method="inverted_cdf"): exact when it falls within cap pixels; otherwise nan with
+                             hd95_exceeds_cap=True (cap is then a lower bound); inf when the rank falls among
+                             edge pixels without a counterpart
+      assd                   the average symmetric surface distance over the pairs with a counterpart: (both
+                             fixed-point sums) / 2^16 / (their number), within 2^-16 px of the true mean
+      boundary_iou[r]        |B_r(pred) & B_r(gt)| / |B_r(pred) | B_r(gt)| for each band radius (Cheng et al. 2021,
+                             Euclidean band)
+    A ratio without a denominator is nan.  boundary_ious_ref / interior_ious_ref are the lists
+    visualization.py:1687-1751 builds, in its order (image, then class) and with its skip rules (a class absent
+    from the image's ground truth adds nothing; a row whose ground-truth set is empty adds nothing), computed
+    without the ignore rule; boundary_iou_ref / interior_iou_ref are their means (nan when empty)."""
+    surf, band, refrows = _host(stats["surf"]), _host(stats["band"]), _host(stats["refrows"])
+    cap, radii = int(stats["cap"]), tuple(stats["band_radii"])
+    cap2 = cap * cap
+    if surf.ndim != 3 or surf.shape[1:] != (2, cap2 + 5) or band.shape != (surf.shape[0], len(radii), 3) or \
+            refrows.ndim != 4 or refrows.shape[1:] != (surf.shape[0], 2, 3):
+        raise ValueError(f"boundary_metrics_from_stats: buffers {surf.shape}, {band.shape}, {refrows.shape} do not "
+                         f"fit cap = {cap} and {len(radii)} radii")
+    k = surf.shape[0]
+    if class_names is None:
+        class_names = CLASS_NAMES[:k]
+    if len(class_names) != k:
+        raise ValueError(f"boundary_metrics_from_stats: {len(class_names)} class names for {k} classes")
+    tolerances = tuple(int(t) for t in tolerances)
+    if any(not 0 <= t <= cap for t in tolerances):
+        raise ValueError(f"boundary_metrics_from_stats: tolerances {tolerances} must lie in 0..cap = {cap}")
+    d2 = np.arange(cap2 + 1)
+    result: Dict = {}
+    for c, name in enumerate(class_names):
+        hist = [surf[c, d, :cap2 + 1].astype(np.int64) for d in (0, 1)]
+        over = [int(surf[c, d, cap2 + 1]) for d in (0, 1)]
+        none = [int(surf[c, d, cap2 + 2]) for d in (0, 1)]
+        n = [int(hist[d].sum()) + over[d] + none[d] for d in (0, 1)]
+        m: Dict = {"n_pred_edge": n[0], "n_gt_edge": n[1], "nsd": {}, "boundary_precision": {},
+                   "boundary_recall": {}, "boundary_f1": {}, "boundary_iou": {}}
+        for t in tolerances:
+            le = [int(hist[d][:t * t + 1].sum()) for d in (0, 1)]
+            m["nsd"][t] = _ratio(le[0] + le[1], n[0] + n[1])
+            pr, rc = _ratio(le[0], n[0]), _ratio(le[1], n[1])
+            m["boundary_precision"][t], m["boundary_recall"][t] = pr, rc
+            m["boundary_f1"][t] = float("nan") if np.isnan(pr) or np.isnan(rc) else \
+                (2 * pr * rc / (pr + rc) if pr + rc > 0 else 0.0)
+        if n[0] + n[1] == 0:
+            m["hd"] = float("nan")
+        elif none[0] or none[1]:
+            m["hd"] = float("inf")
+        else:
+            m["hd"] = float(np.sqrt(float(max(int(surf[c, 0, cap2 + 3]), int(surf[c, 1, cap2 + 3])))))
+        hd95, exceeds = float("nan"), False
+        per_dir = []
+        for d in (0, 1):
+            if n[d] == 0:
+                continue
+            rank = _percentile_rank(n[d], 0.95)
+            cum = np.cumsum(hist[d])
+            if rank <= cum[-1]:
+                per_dir.append(float(np.sqrt(float(d2[np.searchsorted(cum, rank)]))))
+            elif rank <= cum[-1] + over[d]:
+                exceeds = True
+            else:
+                per_dir.append(float("inf"))
+        if per_dir and (not exceeds or max(per_dir) == float("inf")):
+            hd95 = max(per_dir)
+            exceeds = False
+        m["hd95"], m["hd95_exceeds_cap"] = hd95, exceeds
+        finite = n[0] + n[1] - none[0] - none[1]
+        m["assd"] = _ratio((int(surf[c, 0, cap2 + 4]) + int(surf[c, 1, cap2 + 4])) / DIST_SCALE, finite)
+        for j, r in enumerate(radii):
+            a, b, both = (int(v) for v in band[c, j])
+            m["boundary_iou"][r] = _ratio(both, a + b - both)
+        result[name] = m
+    lists = ([], [])
+    for img in range(refrows.shape[0]):
+        for c in range(k):
+            if refrows[img, c, 0, 1] == 0:  # no pixel of the class in this ground truth: its dilation is empty too
+                continue
+            for row in (0, 1):
+                a, b, both = (int(v) for v in refrows[img, c, row])
+                if b > 0:
+                    lists[row].append(both / (a + b - both))
+    result["boundary_ious_ref"], result["interior_ious_ref"] = lists
+    result["boundary_iou_ref"] = float(np.mean(lists[0])) if lists[0] else float("nan")
+    result["interior_iou_ref"] = float(np.mean(lists[1])) if lists[1] else float("nan")
+    return result
+
+
 def calculate_viability_metrics(pred_live_count: int, pred_dead_count: int, gt_live_count: int,
                                 gt_dead_count: int) -> Dict[str, float]:
     pred_total = pred_live_count + pred_dead_count

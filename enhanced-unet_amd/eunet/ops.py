@@ -28,8 +28,8 @@ DISPATCHED: dict = {}
 
 
 def _dispatched(kinds: str, returns_tensor: bool = False):
-    """kinds: one token per parameter -- A (Act), T (tensor), i (int), f (float), b (bool), d (torch dtype),
-    s (str); A! / T! mark the arguments the op writes, a trailing ? an optional (None-able) argument."""
+    """kinds: one token per parameter -- A (Act), T (tensor), i (int), I (list of int), f (float), b (bool),
+    d (torch dtype), s (str); A! / T! mark the arguments the op writes, a trailing ? an optional (None-able) argument."""
     import inspect
     import string
 
@@ -51,7 +51,8 @@ def _dispatched(kinds: str, returns_tensor: bool = False):
                 ty = f"Tensor({next(letters)}!){q}" if w else f"Tensor{q}"
                 parts += [f"{ty} {nm}"] + ([f"int {nm}_coff", f"int {nm}_c"] if base == "A" else [])
             else:
-                parts.append({"i": "int", "f": "float", "b": "bool", "d": "ScalarType", "s": "str"}[base] + f"{q} {nm}")
+                ty = {"i": "int", "I": "int[]", "f": "float", "b": "bool", "d": "ScalarType", "s": "str"}[base]
+                parts.append(f"{ty}{q} {nm}")
         _LIB.define(f"{fn.__name__}({', '.join(parts)}) -> {'Tensor' if returns_tensor else '()'}")
 
         def impl(*flat):
@@ -979,6 +980,137 @@ def score_hist(probs, mask, edges, ignore_index: int = 255, out=None):
                 raise ValueError(f"score_hist: out {name} must be a contiguous int64 {shape} on {probs.device}")
     _score_hist_op(probs, mask, e, int(ignore_index), hist, invalid)
     return hist, invalid
+
+
+# ---- exact distance transform and boundary statistics (boundary.hip) ------------------------
+EDT_MODES = {"eq": _lib.EDT_EQ, "ne": _lib.EDT_NE, "edge": _lib.EDT_EDGE}  # EUNET_EDT_*
+EDT_NONE = _lib.EDT_NONE
+
+
+@_dispatched("T I i T!")
+def distance_transform_sq(labels, values, mode, out):
+    n, h, w = labels.shape
+    vals = (_lib.c_int64 * len(values))(*values)
+    # the column pass reads the map (with its neighbours from cache) and writes and re-reads the plane; the row
+    # pass reads and writes it once more
+    with kprof.timed("edt_sq", 0.0, len(values) * labels.numel() * (8.0 + 4 * 4.0)):
+        call("eunet_edt_sq", _ptr(labels), n, h, w, vals, len(values), mode, _ptr(out), _stream())
+
+
+_distance_transform_sq_op = distance_transform_sq  # torch.ops.eunet.distance_transform_sq writes into out
+
+
+def _int64_maps(name, what, t, device=None):
+    """t as a contiguous int64 [n, h, w] device map within the transform's limits (and whether it came as [h, w])."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: {what} must be a tensor")
+    if not t.is_cuda or (device is not None and t.device != device):
+        raise ValueError(f"{name}: {what} must live on {'one GPU' if device is None else device}, got {t.device}")
+    if t.dtype != torch.int64:
+        raise ValueError(f"{name}: {what} must be int64, got {t.dtype}")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"{name}: {what} must be [h, w] or [n, h, w], got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous")
+    single = t.dim() == 2
+    if single:
+        t = t.unsqueeze(0)
+    n, h, w = t.shape
+    if not (1 <= n <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE):
+        raise ValueError(f"{name}: {what} {tuple(t.shape)} is outside n 1..65535, h and w 1..{_lib.EDT_MAX_SIDE}")
+    return t, single
+
+
+def _int_list(name, what, xs, lo, hi, nmin, nmax):
+    import operator
+    try:
+        out = [operator.index(x) for x in xs]
+    except TypeError:
+        raise ValueError(f"{name}: {what} must be a sequence of integers, got {xs!r}") from None
+    if not nmin <= len(out) <= nmax or any(not lo <= x <= hi for x in out):
+        raise ValueError(f"{name}: {what} must be {nmin}..{nmax} integers in [{lo}, {hi}], got {xs!r}")
+    return out
+
+
+def _out_buffer(name, what, t, shape, dtype, device):
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or \
+            not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name}: out {what} must be a contiguous {dtype} {tuple(shape)} on {device}")
+    return t
+
+
+def distance_transform_sq(labels, values, mode: str = "eq", out=None):
+    """labels int64 [n, h, w] or [h, w], values 1..8 integers -> int32 [n, nv, h, w] (or [nv, h, w]): the exact
+    squared Euclidean distance of every pixel to the nearest site of its own sample, the sites of plane j being
+    the pixels equal to values[j] (mode "eq"), different from it ("ne") or on its edge ("edge": equal, with a
+    4-neighbour that is not, or that lies outside the image).  A sample without a site is EDT_NONE (INT32_MAX)
+    everywhere.  h, w <= 8192.  out: the buffer to write (include/eunet.h, eunet_edt_sq)."""
+    name = "distance_transform_sq"
+    if mode not in EDT_MODES:
+        raise ValueError(f"{name}: mode must be one of {sorted(EDT_MODES)}, not {mode!r}")
+    t, single = _int64_maps(name, "labels", labels)
+    vals = _int_list(name, "values", values, -2 ** 63, 2 ** 63 - 1, 1, _lib.EDT_MAX_VALUES)
+    n, h, w = t.shape
+    shape = (len(vals), h, w) if single else (n, len(vals), h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=t.device)
+    else:
+        _out_buffer(name, "", out, shape, torch.int32, t.device)
+    _distance_transform_sq_op(t, vals, EDT_MODES[mode], out)
+    return out
+
+
+@_dispatched("T T i i i I T! T! T!? T!")
+def boundary_stats(pred, gt, k, ignore_index, cap, radii, ws, surf, band, refrows):
+    n, h, w = pred.shape
+    rr = (c_int * max(len(radii), 1))(*radii)
+    # two transforms, the 13-pixel pass over both maps and the statistics pass over maps and transforms
+    with kprof.timed("boundary_stats", 0.0, pred.numel() * (2 * k * (8.0 + 4 * 4.0) + 16.0 + k * 24.0)):
+        call("eunet_boundary_stats", _ptr(pred), _ptr(gt), n, h, w, k, ignore_index, cap, rr, len(radii), _ptr(ws),
+             _ptr(surf), _ptr(band), _ptr(refrows), _stream())
+
+
+_boundary_stats_op = boundary_stats  # torch.ops.eunet.boundary_stats adds into surf, band and refrows
+
+
+def boundary_workspace_bytes(n, k, h, w):
+    b = c_size_t()
+    call("eunet_boundary_workspace_bytes", n, k, h, w, ctypes.byref(b))
+    return b.value
+
+
+def boundary_stats(pred, gt, num_classes: int = 3, ignore_index: int = 255, cap: int = 64, band_radii=(2,), out=None):
+    """pred, gt int64 [h, w] or [n, h, w] -> (surf int64 [k, 2, cap^2 + 5], band int64 [k, nr, 3], refrows int64
+    [n, k, 2, 3]): the edge-to-edge squared-distance histograms of both directions with their overflow and
+    no-edge counts, maximum and fixed-point distance sum; the Boundary-IoU band counts for each radius; the
+    reference's boundary and interior set counts per image (include/eunet.h, eunet_boundary_stats).  A pixel whose
+    gt is ignore_index is ignored in pred too, except in refrows.  out = (surf, band, refrows) is added to (the
+    maximum is combined by max); None allocates zeroed ones."""
+    name = "boundary_stats"
+    p, _ = _int64_maps(name, "pred", pred)
+    g, _ = _int64_maps(name, "gt", gt, p.device)
+    if p.shape != g.shape:
+        raise ValueError(f"{name}: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in shape")
+    k, cap = int(num_classes), int(cap)
+    if not 1 <= k <= 3:
+        raise ValueError(f"{name}: num_classes must be 1..3, not {num_classes}")
+    if not 1 <= cap <= _lib.BOUNDARY_MAX_CAP:
+        raise ValueError(f"{name}: cap must be 1..{_lib.BOUNDARY_MAX_CAP}, not {cap}")
+    if not -2 ** 31 <= int(ignore_index) < 2 ** 31:
+        raise ValueError(f"{name}: ignore_index {ignore_index} is not an int32")
+    radii = _int_list(name, "band_radii", band_radii, 0, 2 ** 31 - 1, 0, _lib.BOUNDARY_MAX_RADII)
+    n, h, w = p.shape
+    shapes = ((k, 2, cap * cap + 5), (k, len(radii), 3), (n, k, 2, 3))
+    if out is None:
+        surf, band, refrows = (torch.zeros(s, dtype=torch.int64, device=p.device) for s in shapes)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 3:
+            raise ValueError(f"{name}: out must be (surf, band, refrows)")
+        surf, band, refrows = (_out_buffer(name, what, t, s, torch.int64, p.device)
+                               for what, t, s in zip(("surf", "band", "refrows"), out, shapes))
+    ws = torch.empty(boundary_workspace_bytes(n, k, h, w) // 4, dtype=torch.int32, device=p.device)
+    _boundary_stats_op(p, g, k, int(ignore_index), cap, radii, ws, surf, band if radii else None, refrows)
+    return surf, band, refrows
 
 
 # ---- overlap-tile inference (tiling.hip; the geometry is eunet.tiling.TilePlan) ----------

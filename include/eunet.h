@@ -596,6 +596,61 @@ int eunet_score_hist(const float* probs, const int64_t* mask, int n, int k, long
                      const float* edges, int bins, int ignore_index, int64_t* hist, int64_t* invalid,
                      void* stream);
 
+/* ---- exact distance transform and boundary statistics (boundary.hip) -----------
+ * What the contour metrics of segmentation rest on (Hausdorff distance and its 95th percentile, average symmetric
+ * surface distance, surface Dice at a tolerance, boundary F1, Boundary IoU), and the two rows of
+ * visualization.py:1687-1751 (plot_boundary_accuracy), which the reference forms on the host with scipy.ndimage.
+ * Maps are int64 [n][h][w]; values are compared in all 64 bits (1 and 1 + 2^32 are different values).
+ *   Region  R_v(M) = {x : M(x) = v}.
+ *   Edge    E_v(M) = the pixels of R_v(M) that have a 4-neighbour which lies outside the image or is not in R_v(M):
+ *           m & ~scipy.ndimage.binary_erosion(m) with scipy's defaults (cross element, border_value=0), the
+ *           convention of MONAI's get_mask_edges.
+ *   Squared distance  D_S(x) = min over q in S, in the same sample, of (x_y - q_y)^2 + (x_x - q_x)^2: an int32,
+ *           exact.  When a sample has no site it is EUNET_EDT_NONE = INT32_MAX everywhere in that sample.
+ * eunet_edt_sq: out int32 [n][nv][h][w], out[i][j] = D_S of sample i for the site set S of values[j] (a HOST
+ *   array of nv = 1..8 values): R_v for EUNET_EDT_EQ, the complement of R_v for EUNET_EDT_NE, E_v for
+ *   EUNET_EDT_EDGE.  1 <= h, w <= 8192 (2 * 8191^2 fits an int32), 1 <= n <= 65535.  Two kernels, no
+ *   workspace (the row pass runs in place), no host synchronisation. */
+#define EUNET_EDT_EQ 0
+#define EUNET_EDT_NE 1
+#define EUNET_EDT_EDGE 2
+#define EUNET_EDT_NONE 2147483647
+#define EUNET_EDT_MAX_VALUES 8
+#define EUNET_EDT_MAX_SIDE 8192
+int eunet_edt_sq(const int64_t* labels, int n, int h, int w, const int64_t* values, int nv, int mode,
+                 int32_t* out, void* stream);
+/* eunet_boundary_stats: the one pass behind every contour metric, for pred and gt int64 [n][h][w] and the classes
+ * c = 0 .. k-1 (k = 1..3).
+ * Ignore rule: a pixel with gt == ignore_index counts as ignore_index in pred as well, before anything else (in
+ *   the kernels' predicate; no copy is written).  The ignored area is therefore one region in both maps, its
+ *   edges coincide at distance 0 and favour neither side.  refrows alone is computed WITHOUT the rule.
+ * All outputs are int64 and are ADDED to, never zeroed (a validation set accumulates into one set of buffers);
+ * the one exception is the maximum, which is combined by max.
+ *   surf [k][2][cap2 + 5], cap2 = cap^2, cap = 1..EUNET_BOUNDARY_MAX_CAP.  Direction 0 visits every x in
+ *     E_c(pred) with d2 = D_{E_c(gt)}(x); direction 1 every x in E_c(gt) with d2 = D_{E_c(pred)}(x).
+ *       [d2] for d2 <= cap2: the number of edge pixels at exactly that squared distance;
+ *       [cap2+1]: the count with cap2 < d2 < NONE;  [cap2+2]: the count with d2 = NONE (the other map has no
+ *       edge of this class in that image);  [cap2+3]: the largest finite d2 (0 when there is none);
+ *       [cap2+4]: the sum over finite d2 of floor(2^16 sqrt(d2)), the integer square root of d2 * 2^32: a pure
+ *       integer function, so the sum is order-free.
+ *   band [k][nr][3], for a HOST array of nr = 0..8 integer radii r >= 0:  B_r(M) = {x in R_c(M) :
+ *     D_{E_c(M)}(x) <= r^2}, the part of the region within r pixels of its own contour; the entries are
+ *     (|B_r(pred)|, |B_r(gt)|, |B_r(pred) & B_r(gt)|): the Boundary IoU of Cheng et al. (2021) with a Euclidean
+ *     band; r = 0 is the contour itself.  band may be null when nr = 0.
+ *   refrows [n][k][2][3], per image (the reference averages per-image ratios), on the maps as they are.
+ *     Row 0, the reference's boundary binary_dilation(m) & ~binary_erosion(m): the pixels whose radius-1 L1
+ *     diamond holds both a pixel of the class and a position that is not of the class or lies outside the image.
+ *     Row 1, the reference's interior binary_erosion(m, iterations=2): the pixels whose whole radius-2 L1 diamond
+ *     is inside the image and of the class.  Each row holds (|pred set|, |gt set|, |both|).
+ * ws: int32 [2][n][k][h][w] of workspace (eunet_boundary_workspace_bytes): the EDGE transforms of both maps.
+ * Limits as eunet_edt_sq's; no host synchronisation, no allocation. */
+#define EUNET_BOUNDARY_MAX_CAP 64
+#define EUNET_BOUNDARY_MAX_RADII 8
+int eunet_boundary_workspace_bytes(int n, int k, int h, int w, size_t* bytes);
+int eunet_boundary_stats(const int64_t* pred, const int64_t* gt, int n, int h, int w, int k, int ignore_index,
+                         int cap, const int* radii, int nr, int32_t* ws, int64_t* surf, int64_t* band,
+                         int64_t* refrows, void* stream);
+
 /* ---- overlap-tile inference (tiling.hip) -------------------------------------
  * Prediction on an image larger than one forward pass (no reference line: the reference's only answer to a
  * large field of view is the resize down to max_size, dataset.py; overlap-tile prediction is the strategy
