@@ -162,6 +162,11 @@ SIGNATURES = {
     "eunet_pairwise_overlap": [_f, c_int, _f, c_int, c_int64, _f, c_void_p],
     "eunet_morph_u8": [_f, _f, _f, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "eunet_label_workspace_bytes": [c_int, c_int, POINTER(c_size_t)],
+    "eunet_watershed_workspace_bytes": [c_int, c_int, c_int, POINTER(c_size_t)],
+    "eunet_watershed_basins": [_f, c_int, c_int, c_int, _f, _f, _f, c_void_p],
+    "eunet_watershed_peaks": [_f, _f, _f, c_int, c_int, c_int, _f, c_int, _f, _f, c_void_p],
+    "eunet_watershed_saddles": [_f, _f, c_int, c_int, c_int, _f, _f, _f, ctypes.c_longlong, _f, c_void_p],
+    "eunet_watershed_relabel": [_f, c_int, c_int, c_int, _f, _f, c_int, _f, _f, c_int, c_void_p],
     "eunet_label_components": [_f, c_int, c_int, _f, _f, _f, c_int, _f, c_void_p],
     "eunet_outer_perimeter": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
     "eunet_mask_eq": [_f, c_int, c_int64, c_int64, _f, _f, c_void_p],

@@ -134,7 +134,7 @@ class Evaluator:
     def __init__(self, model, device, model_name, preprocess: Union[str, Callable, None] = "reference", *,
                  activation: str = "softmax", threshold: float = 0.5, tile: Optional[int] = None,
                  tile_blend: str = "crop", tile_margin: Optional[int] = None, tile_overlap: float = 0.25,
-                 tile_batch: int = 4):
+                 tile_batch: int = 4, split: str = "erosion", split_depth: float = 1.0):
         """tile: None (one forward per view, as the reference) or the largest tile side, a multiple of 32: a
         view whose padded height or width exceeds it is predicted tile by tile (eunet.tiling.plan with blend
         tile_blend, margin tile_margin for "crop" -- None: tiling.RECEPTIVE_MARGIN, for which the result is
@@ -144,7 +144,16 @@ class Evaluator:
         activation "softmax" is the reference's path.  "sigmoid" is the prediction path of a model trained
         with losses.bce_dice_loss: a sigmoid per logit (ops.sigmoid_crop), the same TTA mean of probabilities,
         then ops.probs_threshold ([p >= threshold] for one logit, the argmax for more); the reference's
-        hand-tuned probs_to_mask rules are softmax-specific and are not applied."""
+        hand-tuned probs_to_mask rules are softmax-specific and are not applied.
+
+        split: how semantic_to_instances separates touching cells.  "erosion" is the reference's ladder of fixed
+        erosions (train_eval.py:697-785).  "watershed" splits each class along the ridges of its exact distance
+        transform (ops.watershed_from_distance): basins whose peak stands less than split_depth pixels above the
+        saddle to a higher neighbour are merged; no area threshold decides what is split."""
+        if split not in ("erosion", "watershed"):
+            raise ValueError(f"split must be 'erosion' or 'watershed', not {split!r}")
+        self.split = split
+        self.split_depth = ops._watershed_depth("split_depth", split_depth)
         if activation not in ("softmax", "sigmoid"):
             raise ValueError(f"activation must be 'softmax' or 'sigmoid', not {activation!r}")
         self.activation = activation
@@ -424,6 +433,35 @@ class Evaluator:
             emit(region, area)
         return next_label
 
+    def _erosion_ids(self, class_mask, min_area: int) -> tuple:
+        """The reference's split of one opened class mask (train_eval.py:686-790): components under 200 px as they
+        are, larger ones through the erosion ladder -> (int32 id map, number of ids)."""
+        dev = class_mask.device
+        markers, num_labels, areas = ops.label_components(class_mask)
+        final = torch.zeros_like(markers)
+        next_label = 1
+        if num_labels:
+            areas = areas.cpu().numpy()
+            table = np.zeros(num_labels, np.int32)
+            for label_id in range(1, num_labels + 1):
+                area = int(areas[label_id - 1])
+                if area < LARGE_REGION:
+                    table[label_id - 1] = next_label
+                    next_label += 1
+                else:
+                    region, _ = ops.mask_eq(markers, label_id)
+                    next_label = self._split_large_region(region, area, final, next_label, min_area)
+            if table.any():  # every small region in one pass; regions are disjoint components
+                ops.relabel_table(markers, ops.upload(table, dev), final)
+        return final, next_label - 1
+
+    def _watershed_ids(self, class_mask) -> tuple:
+        """The distance-transform watershed of one opened class mask -> (int32 id map, number of ids): every region
+        is 8-connected, so outer_perimeter applies to it as it does to the erosion pieces."""
+        dist = ops.distance_transform_sq(class_mask.long(), [1], "ne")[0]
+        ids, counts, _ = ops.watershed_from_distance(dist, self.split_depth)
+        return ids, _count(counts)
+
     def semantic_to_instances(self, semantic_mask, min_area: int = 3) -> tuple:
         """Semantic mask [h, w] (numpy or tensor; 1 live, 2 dead) -> (instance_masks, instance_labels,
         instance_scores) as the reference returns them; the masks are [h, w] uint8 device tensors (the
@@ -440,23 +478,10 @@ class Evaluator:
             if _count(cnt) == 0:
                 continue
             class_mask = ops.morph_u8(ops.morph_u8(class_mask, 2, False), 2, True)  # MORPH_OPEN, 2x2
-            markers, num_labels, areas = ops.label_components(class_mask)
-            final = torch.zeros_like(markers)
-            next_label = 1
-            if num_labels:
-                areas = areas.cpu().numpy()
-                table = np.zeros(num_labels, np.int32)
-                for label_id in range(1, num_labels + 1):
-                    area = int(areas[label_id - 1])
-                    if area < LARGE_REGION:
-                        table[label_id - 1] = next_label
-                        next_label += 1
-                    else:
-                        region, _ = ops.mask_eq(markers, label_id)
-                        next_label = self._split_large_region(region, area, final, next_label, min_area)
-                if table.any():  # every small region in one pass; regions are disjoint components
-                    ops.relabel_table(markers, ops.upload(table, dev), final)
-            num_final = next_label - 1
+            if self.split == "watershed":
+                final, num_final = self._watershed_ids(class_mask)
+            else:
+                final, num_final = self._erosion_ids(class_mask, min_area)
             if num_final:
                 stats = ops.outer_perimeter(final, num_final).cpu().numpy()
                 lo, hi = max(MIN_AREA_CLASS[class_id], min_area), MAX_AREA

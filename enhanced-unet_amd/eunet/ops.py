@@ -1344,6 +1344,182 @@ def expand_labels(labels, table, m: int):
     return out
 
 
+# ---- distance-transform watershed (watershed.hip) ---------------------------------------------
+def merge_basins(peak, root, offs, a, b, saddle, depth: float):
+    """The host half of the watershed (include/eunet.h, "distance-transform watershed"), over the basin graph of all
+    planes at once: peak / root int arrays [nb] (D at, and plane index of, each basin's root; the basins of plane q
+    are the slots offs[q] .. offs[q + 1] - 1, in raster order of their first pixel), edges (a[e], b[e]) with
+    saddle[e].  The edges are visited by (-saddle, smaller root, larger root); the set whose representative (its
+    member root of largest key (D, -index)) has the smaller key joins the other when sqrt(its peak) -
+    sqrt(saddle) < depth.  Returns (table int32 [nb]: the final id of every basin, 1..m per plane in raster order
+    of each set's first pixel; m int64 [p])."""
+    import math
+
+    import numpy as np
+    peak, root = np.asarray(peak, np.int64), np.asarray(root, np.int64)
+    a, b, saddle = np.asarray(a, np.int64), np.asarray(b, np.int64), np.asarray(saddle, np.int64)
+    nb = len(peak)
+    par = list(range(nb))
+
+    def find(x):
+        while par[x] != x:
+            par[x] = par[par[x]]
+            x = par[x]
+        return x
+
+    if len(a):
+        ra, rb = root[a], root[b]
+        # edges of different planes never share a set, so their mutual order is free; within a plane this is the
+        # order of the definition (the slot breaks the ties between planes, to keep the order total)
+        order = np.lexsort((a, np.maximum(ra, rb), np.minimum(ra, rb), -saddle))
+        pk, rt = peak.tolist(), root.tolist()
+        ea, eb, es = a.tolist(), b.tolist(), saddle.tolist()
+        for e in order.tolist():
+            x, y = find(ea[e]), find(eb[e])
+            if x == y:
+                continue
+            lo, hi = (x, y) if (pk[x], -rt[x]) < (pk[y], -rt[y]) else (y, x)
+            if math.sqrt(pk[lo]) - math.sqrt(es[e]) < depth:
+                par[lo] = hi
+    table = np.zeros(nb, np.int32)
+    m = np.zeros(len(offs) - 1, np.int64)
+    for q in range(len(offs) - 1):
+        seen, nxt = {}, 0
+        for g in range(int(offs[q]), int(offs[q + 1])):  # ascending first pixel: a set is met at its first pixel
+            r = find(g)
+            t = seen.get(r)
+            if t is None:
+                nxt += 1
+                seen[r] = t = nxt
+            table[g] = t
+        m[q] = nxt
+    return table, m
+
+
+def _watershed_depth(name, depth):
+    try:
+        d = float(depth)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: depth must be a number of pixels, got {depth!r}") from None
+    if d != d or d < 0.0:
+        raise ValueError(f"{name}: depth must be >= 0 (inf allowed), got {depth!r}")
+    return d
+
+
+def watershed_from_distance(dist_sq, depth: float = 1.0, out=None, _table_capacity=None):
+    """dist_sq int32 [h, w] or [p, h, w] of squared distances (foreground: > 0; what distance_transform_sq gives in
+    mode "ne") -> (ids int32 of the same shape, counts int64 [p] on the device, areas int32 [p, max(counts)] on the
+    device, zero past a plane's count; [max] for an [h, w] input): the basins of each plane, those merged whose
+    peak stands less than `depth` pixels above the saddle to a higher neighbour, numbered 1..counts[plane] in raster
+    order of each region's first pixel, background 0 (include/eunet.h, "distance-transform watershed"; depth 0: every
+    basin, inf: the 8-connected components).  The basin graph is merged on the host (merge_basins): the call
+    synchronises.  out: the ids buffer to write.  _table_capacity: the first size of the saddle hash table (a power
+    of two; it is doubled until every pair fits), for tests."""
+    import numpy as np
+    name = "watershed_from_distance"
+    if not isinstance(dist_sq, torch.Tensor):
+        raise ValueError(f"{name}: dist_sq must be a tensor")
+    if not dist_sq.is_cuda:
+        raise ValueError(f"{name}: dist_sq must live on a GPU, got {dist_sq.device}")
+    if dist_sq.dtype != torch.int32:
+        raise ValueError(f"{name}: dist_sq must be int32, got {dist_sq.dtype}")
+    if dist_sq.dim() not in (2, 3):
+        raise ValueError(f"{name}: dist_sq must be [h, w] or [p, h, w], got {tuple(dist_sq.shape)}")
+    if not dist_sq.is_contiguous():
+        raise ValueError(f"{name}: dist_sq must be contiguous")
+    single = dist_sq.dim() == 2
+    d = dist_sq.unsqueeze(0) if single else dist_sq
+    p, h, w = d.shape
+    if not (1 <= p <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE and p * h * w < 2 ** 31):
+        raise ValueError(f"{name}: dist_sq {tuple(dist_sq.shape)} is outside p 1..65535, h and w "
+                         f"1..{_lib.EDT_MAX_SIDE}, p h w < 2^31")
+    depth = _watershed_depth(name, depth)
+    if _table_capacity is None:
+        cap = None
+    else:
+        cap = int(_table_capacity)
+        if cap < 2 or cap > 2 ** 30 or cap & (cap - 1):
+            raise ValueError(f"{name}: _table_capacity must be a power of two in 2..2^30, got {_table_capacity!r}")
+    dev = d.device
+    if out is None:
+        ids = torch.empty(tuple(dist_sq.shape), dtype=torch.int32, device=dev)
+    else:
+        ids = _out_buffer(name, "", out, tuple(dist_sq.shape), torch.int32, dev)
+        if ids.data_ptr() == dist_sq.data_ptr():
+            raise ValueError(f"{name}: out must not be dist_sq")
+    hw = h * w
+    nbytes = c_size_t()
+    call("eunet_watershed_workspace_bytes", p, h, w, ctypes.byref(nbytes))
+    ws = torch.empty(nbytes.value // 4, dtype=torch.int32, device=dev)
+    counts32 = torch.empty(p, dtype=torch.int32, device=dev)
+    # up reads the plane and writes the parents; a jump round reads and writes them; first / count / rank / fill
+    # read roots and firsts and write the basins
+    with kprof.timed("watershed_basins", 0.0, p * hw * 4.0 * 12):
+        call("eunet_watershed_basins", _ptr(d), p, h, w, _ptr(ids), _ptr(counts32), _ptr(ws), _stream())
+    nb = counts32.cpu().numpy().astype(np.int64)
+    offs = np.concatenate([[0], np.cumsum(nb)])
+    nb_total = int(offs[-1])
+    if nb_total == 0:  # no foreground anywhere: the basin map is all background already
+        areas = torch.zeros((0,) if single else (p, 0), dtype=torch.int32, device=dev)
+        return ids, torch.zeros(p, dtype=torch.int64, device=dev), areas
+    offs_d = upload(offs[:-1].astype(np.int32), dev)
+    rootpeak = torch.empty(2, nb_total, dtype=torch.int32, device=dev)
+    with kprof.timed("watershed_peaks", 0.0, p * hw * 4.0):
+        call("eunet_watershed_peaks", _ptr(d), _ptr(ids), _ptr(ws), p, h, w, _ptr(offs_d), nb_total, _ptr(rootpeak[0]),
+             _ptr(rootpeak[1]), _stream())
+    if cap is None:  # about 2.5 pairs per basin at most on noise; 8 slots per basin keep the probes short
+        cap = 64
+        while cap < 8 * nb_total:
+            cap *= 2
+    while True:
+        keys = torch.empty(cap, dtype=torch.int64, device=dev)
+        vals = torch.empty(cap + 1, dtype=torch.int32, device=dev)  # [cap]: the overflow count
+        with kprof.timed("watershed_saddles", 0.0, p * hw * 4.0 * 10):
+            call("eunet_watershed_saddles", _ptr(d), _ptr(ids), p, h, w, _ptr(offs_d), _ptr(keys), _ptr(vals), cap,
+                 _ptr(vals[cap:]), _stream())
+        v = vals.cpu().numpy()
+        if v[cap] == 0:
+            break
+        if cap >= 2 ** 30:
+            raise _lib.EunetError(f"{name}: the saddle table overflows at 2^30 slots")
+        cap *= 2  # nothing was dropped silently: the pass is run again with room for every pair
+    k = keys.cpu().numpy()
+    used = k != -1
+    rp = rootpeak.cpu().numpy()
+    table, m = merge_basins(rp[1], rp[0], offs, k[used] >> 32, k[used] & 0xffffffff, v[:cap][used], depth)
+    amax = int(m.max())
+    areas = torch.empty(p, amax, dtype=torch.int32, device=dev)
+    with kprof.timed("watershed_relabel", 0.0, p * hw * 4.0 * 2):
+        call("eunet_watershed_relabel", _ptr(ids), p, h, w, _ptr(offs_d), _ptr(upload(table, dev)), nb_total, _ptr(ids),
+             _ptr(areas), amax, _stream())
+    return ids, upload(m, dev), areas[0] if single else areas
+
+
+def watershed_split(labels, values, depth: float = 1.0, out=None):
+    """labels int64 [n, h, w] or [h, w], values 1..8 integers -> (ids int32 [n, nv, h, w] (or [nv, h, w]), counts int64
+    [n, nv] (or [nv]), areas int32 [n, nv, max count] (or [nv, max count])): plane j splits the region labels ==
+    values[j] of each sample along the ridges of its distance to the rest, distance_transform_sq(labels, values,
+    "ne") followed by watershed_from_distance.  out: the ids buffer to write."""
+    name = "watershed_split"
+    depth = _watershed_depth(name, depth)
+    t, single = _int64_maps(name, "labels", labels)
+    vals = _int_list(name, "values", values, -2 ** 63, 2 ** 63 - 1, 1, _lib.EDT_MAX_VALUES)
+    n, h, w = t.shape
+    nv = len(vals)
+    if n * nv > 65535 or n * nv * h * w >= 2 ** 31:
+        raise ValueError(f"{name}: {n} x {nv} planes of {h} x {w} exceed 65535 planes or 2^31 pixels")
+    shape = (nv, h, w) if single else (n, nv, h, w)
+    if out is not None:
+        _out_buffer(name, "", out, shape, torch.int32, t.device)
+    dist = distance_transform_sq(t, vals, "ne")
+    ids, counts, areas = watershed_from_distance(dist.view(n * nv, h, w), depth,
+                                                 out=None if out is None else out.view(n * nv, h, w))
+    ids = ids.view(shape) if out is None else out
+    if single:
+        return ids, counts, areas
+    return ids, counts.view(n, nv), areas.view(n, nv, areas.shape[-1])
+
+
 # ---- dual-branch fusion (fusion.hip) -------------------------------------------------
 def fusion_tiles(n, h, w):
     t, gt = c_int(), c_int()

@@ -457,7 +457,8 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
  * eunet_debug_enabled: 1 in the debug build, 0 in the release library (where the checks compile away).
  * eunet_debug_status: synchronises the device; *count = failed checks since the last reset,
  * *unit_line = unit * 100000 + source line of the first (units: 1 capi, 2 conv3x3, 3 bn_pool_up,
- * 4 head, 5 instances, 6 baselines, 7 upconv, 8 bce_dice, 9 weightmap, 10 tiling, 11 warp; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
+ * 4 head, 5 instances, 6 baselines, 7 upconv, 8 bce_dice, 9 weightmap, 10 tiling, 11 warp,
+ * 12 boundary, 13 watershed; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
 int eunet_debug_enabled(void);
 int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset);
 int eunet_debug_selftest(void* stream);
@@ -650,6 +651,51 @@ int eunet_boundary_workspace_bytes(int n, int k, int h, int w, size_t* bytes);
 int eunet_boundary_stats(const int64_t* pred, const int64_t* gt, int n, int h, int w, int k, int ignore_index,
                          int cap, const int* radii, int nr, int32_t* ws, int64_t* surf, int64_t* band,
                          int64_t* refrows, void* stream);
+
+/* ---- distance-transform watershed (watershed.hip) ------------------------------
+ * Splits touching cells along the ridges of a squared-distance map (train_eval.py:654-850: the docstring of
+ * semantic_to_instances promises a watershed; the reference runs a ladder of fixed erosions).  The definition is
+ * integer and order-free.  Input: planes D int32 [p][h][w] of squared distances, what eunet_edt_sq gives in mode
+ * EUNET_EDT_NE: foreground is D > 0, a plane without background holds EUNET_EDT_NONE.
+ *   Ascent  key(q) = (D[q], -q), q the linear index in the plane, compared lexicographically.  up(q) = the
+ *           foreground pixel of largest key among q and its 8 neighbours inside the image.  Keys strictly increase
+ *           along up, so every foreground pixel reaches one root (a local key maximum); a basin is the set of
+ *           pixels of one root, its peak is D[root].  Plateaus resolve by the index alone.
+ *   Saddle  of two basins a != b: the maximum, over the pairs of 8-adjacent pixels x in a, y in b, of
+ *           min(D[x], D[y]).
+ *   Merge   on the host (eunet.ops.merge_basins): the saddle edges sorted by (-saddle, min(a, b), max(a, b)) in
+ *           root indices; a union-find whose representative is the member root of largest key; for an edge whose
+ *           ends lie in different sets, lo = the set with the smaller representative key joins the other when
+ *           sqrt(D[lo]) - sqrt(saddle) < depth (fp64, depth in pixels).  depth 0 merges nothing, depth inf leaves
+ *           the 8-connected components.
+ *   Ids     sets numbered 1..m per plane in raster order of each set's first pixel (eunet_label_components'
+ *           convention), background 0.
+ * Limits: 1 <= h, w <= 8192, 1 <= p <= 65535, p h w < 2^31.  ws: eunet_watershed_workspace_bytes; it carries the
+ * roots from eunet_watershed_basins to eunet_watershed_peaks.
+ * eunet_watershed_basins: basin int32 [p][h][w] = the basins numbered 1..counts[plane] in raster order of each
+ *   basin's first pixel, background 0; counts int32 [p].  Adjacent foreground pixels are never both roots, so
+ *   counts[plane] <= ceil(h / 2) ceil(w / 2).  No host synchronisation: pointer jumping runs its ceil(log2(h w)) + 1
+ *   rounds as launches that return at once after the first round that changed nothing.
+ * eunet_watershed_peaks: with offs int32 [p] (device) = the exclusive prefix sum of counts and nb_total their sum,
+ *   root[offs[plane] + b - 1] = the root pixel of basin b of that plane (index in the plane), peak[...] = its D.
+ * eunet_watershed_saddles: fills an open-addressing hash table of `capacity` slots (a power of two >= 2):
+ *   keys int64 [capacity] = (a << 32) | b with a < b the slots of eunet_watershed_peaks, -1 where empty; vals int32
+ *   [capacity] = the pair's saddle.  The call clears the table first.  An insert that finds
+ *   min(capacity, 64) successive slots taken adds one to *overflow (device int32) and stores nothing: when
+ *   *overflow != 0 the table is incomplete and the call is repeated with a larger one.
+ * eunet_watershed_relabel: ids[i] = table[offs[plane] + basin[i] - 1] on the foreground (table: device int32
+ *   [nb_total] of ids 1..amax), 0 elsewhere; ids may be basin itself.  areas int32 [p][amax] is zeroed and counts
+ *   the pixels of every id. */
+#define EUNET_WATERSHED_FLAG_WORDS 32
+int eunet_watershed_workspace_bytes(int p, int h, int w, size_t* bytes);
+int eunet_watershed_basins(const int32_t* dist, int p, int h, int w, int32_t* basin, int32_t* counts, int32_t* ws,
+                           void* stream);
+int eunet_watershed_peaks(const int32_t* dist, const int32_t* basin, const int32_t* ws, int p, int h, int w,
+                          const int32_t* offs, int nb_total, int32_t* root, int32_t* peak, void* stream);
+int eunet_watershed_saddles(const int32_t* dist, const int32_t* basin, int p, int h, int w, const int32_t* offs,
+                            int64_t* keys, int32_t* vals, long long capacity, int32_t* overflow, void* stream);
+int eunet_watershed_relabel(const int32_t* basin, int p, int h, int w, const int32_t* offs, const int32_t* table,
+                            int nb_total, int32_t* ids, int32_t* areas, int amax, void* stream);
 
 /* ---- overlap-tile inference (tiling.hip) -------------------------------------
  * Prediction on an image larger than one forward pass (no reference line: the reference's only answer to a
