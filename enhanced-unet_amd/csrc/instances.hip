@@ -332,20 +332,21 @@ __global__ __launch_bounds__(NT) void cc_init_kernel(const V* v, long long total
     parent[i] = v[i] != 0 ? (int)i : -1;
 }
 
-template <typename V, bool BYVALUE>
+// CONN = 4: W and N only (scipy.ndimage.label's default structure).
+template <typename V, bool BYVALUE, int CONN = 8>
 __global__ __launch_bounds__(NT) void cc_merge_kernel(const V* v, int h, int w, int* parent) {
   const long long total = (long long)h * w;
   for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
     if (v[i] == 0) continue;
     const int x = (int)(i % w), y = (int)(i / w);
-    // the four neighbours that precede i in raster order: W, NW, N, NE
+    // the neighbours that precede i in raster order: W, NW, N, NE (W and N when CONN == 4)
     if (x > 0 && same_comp<V, BYVALUE>(v, i, i - 1)) uf_unite(parent, (int)i, (int)(i - 1));
     if (y > 0) {
       const long long up = i - w;
       EUNET_DASSERT(up >= 0 && up + 1 < total);
-      if (x > 0 && same_comp<V, BYVALUE>(v, i, up - 1)) uf_unite(parent, (int)i, (int)(up - 1));
+      if (CONN == 8 && x > 0 && same_comp<V, BYVALUE>(v, i, up - 1)) uf_unite(parent, (int)i, (int)(up - 1));
       if (same_comp<V, BYVALUE>(v, i, up)) uf_unite(parent, (int)i, (int)up);
-      if (x + 1 < w && same_comp<V, BYVALUE>(v, i, up + 1)) uf_unite(parent, (int)i, (int)(up + 1));
+      if (CONN == 8 && x + 1 < w && same_comp<V, BYVALUE>(v, i, up + 1)) uf_unite(parent, (int)i, (int)(up + 1));
     }
   }
 }
@@ -589,12 +590,12 @@ __global__ __launch_bounds__(NT) void expand_labels_kernel(const int* labels, lo
   }
 }
 
-template <typename V, bool BYVALUE>
+template <typename V, bool BYVALUE, int CONN = 8>
 void launch_components(const V* v, int h, int w, int* parent, hipStream_t s) {
   const long long total = (long long)h * w;
   const unsigned g = grid_for(total);
   cc_init_kernel<V><<<g, NT, 0, s>>>(v, total, parent);
-  cc_merge_kernel<V, BYVALUE><<<g, NT, 0, s>>>(v, h, w, parent);
+  cc_merge_kernel<V, BYVALUE, CONN><<<g, NT, 0, s>>>(v, h, w, parent);
   cc_compress_kernel<<<g, NT, 0, s>>>(total, parent);
 }
 
@@ -604,6 +605,24 @@ bool zero_async(void* p, size_t bytes, hipStream_t s, const char* what) {
     return false;
   }
   return true;
+}
+
+// the labelling behind eunet_label_components (CONN 8) and eunet_label_components_conn; the arguments are checked
+template <int CONN>
+int label_components_impl(const uint8_t* img, int h, int w, int32_t* labels, int32_t* n_out, int32_t* areas,
+                          int areas_cap, int32_t* ws, hipStream_t s, const char* what) {
+  const long long total = (long long)h * w;
+  if (!zero_async(areas, sizeof(int32_t) * (size_t)areas_cap, s, what)) return EUNET_ERR_HIP;
+  int* parent = ws;
+  int* block_count = ws + total;
+  const long long nb = (total + NT - 1) / NT;
+  launch_components<uint8_t, false, CONN>(img, h, w, parent, s);
+  cc_count_roots_kernel<<<(unsigned)nb, NT, 0, s>>>(parent, total, block_count);
+  cc_scan_blocks_kernel<<<1, NT, 0, s>>>(block_count, (int)nb, n_out);
+  cc_rank_roots_kernel<<<(unsigned)nb, NT, 0, s>>>(parent, total, block_count, labels);
+  cc_relabel_kernel<<<grid_for(total), NT, 0, s>>>(parent, total, labels, areas, areas_cap);
+  EUNET_LAUNCH_CHECK(what);
+  return EUNET_OK;
 }
 
 }  // namespace
@@ -728,18 +747,28 @@ int eunet_label_components(const uint8_t* img, int h, int w, int32_t* labels, in
   // an 8-connected component owns at least one cell of every 2 x 2 block grid it touches
   EUNET_REQUIRE(areas_cap >= (long long)((h + 1) / 2) * ((w + 1) / 2),
                 "label_components: areas needs ceil(h/2) * ceil(w/2) entries");
-  hipStream_t s = (hipStream_t)stream;
-  if (!zero_async(areas, sizeof(int32_t) * (size_t)areas_cap, s, "label_components")) return EUNET_ERR_HIP;
-  int* parent = ws;
-  int* block_count = ws + total;
-  const long long nb = (total + NT - 1) / NT;
-  launch_components<uint8_t, false>(img, h, w, parent, s);
-  cc_count_roots_kernel<<<(unsigned)nb, NT, 0, s>>>(parent, total, block_count);
-  cc_scan_blocks_kernel<<<1, NT, 0, s>>>(block_count, (int)nb, n_out);
-  cc_rank_roots_kernel<<<(unsigned)nb, NT, 0, s>>>(parent, total, block_count, labels);
-  cc_relabel_kernel<<<grid_for(total), NT, 0, s>>>(parent, total, labels, areas, areas_cap);
-  EUNET_LAUNCH_CHECK("label_components");
-  return EUNET_OK;
+  return label_components_impl<8>(img, h, w, labels, n_out, areas, areas_cap, ws, (hipStream_t)stream,
+                                  "label_components");
+}
+
+int eunet_label_components_conn(const uint8_t* img, int h, int w, int32_t* labels, int32_t* n_out, int32_t* areas,
+                                int areas_cap, int32_t* ws, int connectivity, void* stream) {
+  EUNET_REQUIRE(img && labels && n_out && areas && ws && h > 0 && w > 0, "label_components_conn: bad args");
+  EUNET_REQUIRE(connectivity == 4 || connectivity == 8, "label_components_conn: connectivity must be 4 or 8 (got %d)",
+                connectivity);
+  const long long total = (long long)h * w;
+  EUNET_REQUIRE(total < (1ll << 31), "label_components_conn: h * w must be below 2^31");
+  if (connectivity == 8) {
+    EUNET_REQUIRE(areas_cap >= (long long)((h + 1) / 2) * ((w + 1) / 2),
+                  "label_components_conn: areas needs ceil(h/2) * ceil(w/2) entries at connectivity 8");
+    return label_components_impl<8>(img, h, w, labels, n_out, areas, areas_cap, ws, (hipStream_t)stream,
+                                    "label_components_conn");
+  }
+  // one pixel of each component, no two of them 4-adjacent: at most one colour of a checkerboard
+  EUNET_REQUIRE(areas_cap >= (total + 1) / 2,
+                "label_components_conn: areas needs ceil(h w / 2) entries at connectivity 4");
+  return label_components_impl<4>(img, h, w, labels, n_out, areas, areas_cap, ws, (hipStream_t)stream,
+                                  "label_components_conn");
 }
 
 int eunet_outer_perimeter(const int32_t* labels, int h, int w, int n, int32_t* stats, int32_t* ws, void* stream) {

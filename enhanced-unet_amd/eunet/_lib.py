@@ -52,6 +52,7 @@ EDT_EQ, EDT_NE, EDT_EDGE = 0, 1, 2  # EUNET_EDT_*
 EDT_NONE = 2 ** 31 - 1
 EDT_MAX_VALUES, EDT_MAX_SIDE = 8, 8192
 BOUNDARY_MAX_CAP, BOUNDARY_MAX_RADII = 64, 8
+PAIRS_MAX_ID = 2 ** 24 - 1  # EUNET_PAIRS_MAX_ID
 
 
 class OptTensor(ctypes.Structure):
@@ -168,6 +169,9 @@ SIGNATURES = {
     "eunet_watershed_saddles": [_f, _f, c_int, c_int, c_int, _f, _f, _f, ctypes.c_longlong, _f, c_void_p],
     "eunet_watershed_relabel": [_f, c_int, c_int, c_int, _f, _f, c_int, _f, _f, c_int, c_void_p],
     "eunet_label_components": [_f, c_int, c_int, _f, _f, _f, c_int, _f, c_void_p],
+    "eunet_label_components_conn": [_f, c_int, c_int, _f, _f, _f, c_int, _f, c_int, c_void_p],
+    "eunet_label_pairs": [_f, c_int, _f, c_int, c_int, c_int, c_int, _f, _f, ctypes.c_longlong, _f, _f, c_void_p],
+    "eunet_labels_from_stack": [_f, c_int, c_int, c_int, _f, _f, _f, _f, c_void_p],
     "eunet_outer_perimeter": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
     "eunet_mask_eq": [_f, c_int, c_int64, c_int64, _f, _f, c_void_p],
     "eunet_mask_and": [_f, _f, c_int64, _f, _f, c_void_p],

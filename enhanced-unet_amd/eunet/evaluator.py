@@ -16,6 +16,11 @@
     .evaluate_with_curves(dataloader, coco_map=False) -> evaluate()'s rows plus auc_ / ap_ / ece_<class>
     .evaluate_boundary(dataloader) -> per-class contour metrics (HD, HD95, ASSD, surface Dice, boundary F1,
         Boundary IoU) and the two lists of visualization.py:1687-1751 (plot_boundary_accuracy)
+    .semantic_to_instance_maps(mask, min_area=3) -> (ids int32 [2,h,w], counts, scores): semantic_to_instances'
+        instances as one id map per class
+    .evaluate_panoptic(dataloader) -> PQ / SQ / DQ, AJI, object Dice, SEG, F1 and AP over IoU 0.5 .. 0.95 per class
+        and pooled, from label maps (no reference counterpart)
+    .evaluate_by_size(dataloader) -> per-object coverage binned by object area (visualization.py:1753-1817)
 
 Every per-pixel step runs in HIP (evalpath.hip): the flips and 0.75/1.25
 rescales (PyTorch bilinear index math), softmax + crop, the TTA mean, the
@@ -63,6 +68,11 @@ statistics pass (ops.boundary_stats, boundary.hip) that accumulates over the loa
 metrics.boundary_metrics_from_stats forms the Hausdorff distance, HD95, the average symmetric surface distance,
 surface Dice, boundary F1 and Boundary IoU, and the reference's boundary / interior IoU lists.
 
+Label-map instance metrics (evaluate_panoptic, evaluate_by_size): the predicted instances and the ground truth are
+two integer id maps per class, and every score is a function of their sparse contingency table, which one pass
+builds on the device (ops.label_pairs, pairs.hip) and metrics.instance_stats_from_pairs reads in integers.  No
+mask plane per instance is expanded and no pair of masks is compared.
+
 Overlap-tile inference (no reference counterpart: the reference resizes every image down to max_size):
 Evaluator(..., tile=T) sends an image whose padded size exceeds T in either axis through the network tile by
 tile (eunet.tiling.plan; ops.tile_gather, forward_lowres on tile_batch tiles at a time, one ops.tile_blend
@@ -81,10 +91,12 @@ import torch
 import torch.nn.functional as F
 
 from . import ops, tiling
-from .metrics import (CLASS_NAMES, _dev_long, boundary_metrics_from_stats, calculate_boundary_stats, calculate_dice,
+from .metrics import (CLASS_NAMES, INSTANCE_CLASSES, PANOPTIC_IOU_PERCENT, SIZE_EDGES, _dev_long, _stack_masks,
+                      add_instance_stats, boundary_metrics_from_stats, calculate_boundary_stats, calculate_dice,
                       calculate_instance_metrics, calculate_iou, calculate_semantic_metrics,
                       calculate_viability_metrics, coco_image_matches, coco_map_from_matches, curve_edges,
-                      curve_metrics_from_hist)
+                      curve_metrics_from_hist, instance_stats_from_pairs, panoptic_keys, panoptic_metrics_from_stats,
+                      size_strata_from_pairs)
 
 TTA_SCALES = (0.75, 1.25)
 
@@ -109,6 +121,8 @@ def curve_keys(class_names) -> tuple:
     return tuple(f"{s}_{name}" for name in class_names for s in CURVE_STATS)
 
 
+# the rows evaluate_panoptic() returns for the default thresholds
+PANOPTIC_KEYS = panoptic_keys() + ("aji_image_mean", "gt_overlap_pixels")
 # the rows evaluate_with_curves() adds for a three-class model (visualization.py:1131, 1184; the ECE of :1847-1864)
 CURVE_KEYS = curve_keys(CLASS_NAMES)
 
@@ -462,17 +476,18 @@ class Evaluator:
         ids, counts, _ = ops.watershed_from_distance(dist, self.split_depth)
         return ids, _count(counts)
 
-    def semantic_to_instances(self, semantic_mask, min_area: int = 3) -> tuple:
-        """Semantic mask [h, w] (numpy or tensor; 1 live, 2 dead) -> (instance_masks, instance_labels,
-        instance_scores) as the reference returns them; the masks are [h, w] uint8 device tensors (the
-        form CellDataset hands out ground truth in), labels 0 live / 1 dead, scores float64."""
+    def _select_instances(self, semantic_mask, min_area: int) -> tuple:
+        """The selection both semantic_to_instances and semantic_to_instance_maps rest on: per class the 2x2 open, the
+        split, the area limits and the score, and the MAX_INSTANCES cut -> (finals {class_id: (the split's int32 id
+        map, the number of ids in it)}, entries [(class_id, id in that map, score)] in the order semantic_to_instances returns them, device,
+        (h, w))."""
         sem = semantic_mask if isinstance(semantic_mask, torch.Tensor) else \
             torch.from_numpy(np.ascontiguousarray(semantic_mask))
         if sem.dtype not in (torch.int32, torch.int64):
             sem = sem.long()
         dev = sem.device if sem.is_cuda else (self.device if str(self.device) != "cpu" else "cuda")
         sem = sem.to(dev).contiguous()
-        instance_masks, instance_labels, instance_scores = [], [], []
+        finals, entries = {}, []
         for class_id in (1, 2):
             class_mask, cnt = ops.mask_eq(sem, class_id)
             if _count(cnt) == 0:
@@ -483,30 +498,137 @@ class Evaluator:
             else:
                 final, num_final = self._erosion_ids(class_mask, min_area)
             if num_final:
+                finals[class_id] = (final, num_final)
                 stats = ops.outer_perimeter(final, num_final).cpu().numpy()
                 lo, hi = max(MIN_AREA_CLASS[class_id], min_area), MAX_AREA
-                slots = np.full(num_final, -1, np.int32)
-                scores = []
                 for k in range(num_final):
                     n_axis, n_diag, area = (int(v) for v in stats[k, :3])
                     if area < lo or area > hi:
                         continue
                     perimeter = _perimeter(n_axis, n_diag)
                     compactness = 4 * np.pi * area / (perimeter ** 2) if perimeter > 0 else 0.5
-                    slots[k] = len(scores)
-                    scores.append(0.7 * min(area / 150.0, 1.0) + 0.3 * compactness)
-                if scores:
-                    planes = ops.expand_labels(final, ops.upload(slots, dev), len(scores))
-                    instance_masks += list(planes)
-                    instance_labels += [class_id - 1] * len(scores)
-                    instance_scores += scores
-            if len(instance_masks) > MAX_INSTANCES:  # inside the class loop, on the combined list (:842-848)
-                keep = sorted(range(len(instance_scores)), key=lambda i: instance_scores[i],
-                              reverse=True)[:MAX_INSTANCES]
-                instance_masks = [instance_masks[i] for i in keep]
-                instance_labels = [instance_labels[i] for i in keep]
-                instance_scores = [instance_scores[i] for i in keep]
-        return instance_masks, instance_labels, instance_scores
+                    entries.append((class_id, k + 1, 0.7 * min(area / 150.0, 1.0) + 0.3 * compactness))
+            if len(entries) > MAX_INSTANCES:  # inside the class loop, on the combined list (:842-848)
+                keep = sorted(range(len(entries)), key=lambda i: entries[i][2], reverse=True)[:MAX_INSTANCES]
+                entries = [entries[i] for i in keep]
+        return finals, entries, dev, tuple(sem.shape)
+
+    def semantic_to_instances(self, semantic_mask, min_area: int = 3) -> tuple:
+        """Semantic mask [h, w] (numpy or tensor; 1 live, 2 dead) -> (instance_masks, instance_labels,
+        instance_scores) as the reference returns them; the masks are [h, w] uint8 device tensors (the
+        form CellDataset hands out ground truth in), labels 0 live / 1 dead, scores float64."""
+        finals, entries, dev, _ = self._select_instances(semantic_mask, min_area)
+        plane_of = {}
+        for class_id, (final, num_final) in finals.items():
+            kept = sorted(k for c, k, _ in entries if c == class_id)
+            if not kept:
+                continue
+            slots = np.full(num_final, -1, np.int32)
+            slots[np.asarray(kept) - 1] = np.arange(len(kept), dtype=np.int32)
+            planes = ops.expand_labels(final, ops.upload(slots, dev), len(kept))
+            plane_of.update({(class_id, k): planes[i] for i, k in enumerate(kept)})
+        return ([plane_of[(c, k)] for c, k, _ in entries], [c - 1 for c, _, _ in entries],
+                [s for _, _, s in entries])
+
+    def semantic_to_instance_maps(self, semantic_mask, min_area: int = 3) -> tuple:
+        """The instances of semantic_to_instances as one id map per class, without a mask plane per instance: (ids
+        int32 [2, h, w] on the device, plane 0 live / 1 dead, background 0; counts [n_live, n_dead]; scores [[float64
+        per live id], [per dead id]], scores[c][id - 1]).  Within a class the instances are numbered 1.. in ascending
+        order of their id in the split's map (ops.relabel_table on that map)."""
+        finals, entries, dev, (h, w) = self._select_instances(semantic_mask, min_area)
+        ids = torch.zeros(2, h, w, dtype=torch.int32, device=dev)
+        counts, scores = [0, 0], [[], []]
+        for class_id, (final, num_final) in finals.items():
+            kept = sorted((k, s) for c, k, s in entries if c == class_id)
+            if not kept:
+                continue
+            table = np.zeros(num_final, np.int32)  # an entry for every id of the map, as relabel_table requires
+            table[np.asarray([k for k, _ in kept]) - 1] = np.arange(1, len(kept) + 1, dtype=np.int32)
+            ops.relabel_table(final, ops.upload(table, dev), ids[class_id - 1])
+            counts[class_id - 1] = len(kept)
+            scores[class_id - 1] = [sc for _, sc in kept]
+        return ids, counts, scores
+
+    # ---- label-map instance metrics (no reference counterpart; the size strata are visualization.py:1753-1817) ----
+    def _label_map_models_only(self, what: str):
+        if self.activation == "sigmoid":
+            raise ValueError(f"{what} is not built for sigmoid models (DESIGN.md §7)")
+        if getattr(self.model, "dual_branch", False):
+            raise ValueError(f"{what} is not built for the dual-branch model (DESIGN.md §7)")
+
+    def _gt_instance_maps(self, item, shape, dev) -> tuple:
+        """A dataset item's instance_masks / instance_labels -> (int32 [2, h, w] id maps, -1 where semantic_mask is
+        255; the pixels more than one instance of a class claims).  Instance j of the item has id j + 1."""
+        masks, labels = item["instance_masks"], [int(l) for l in item["instance_labels"]]
+        sem = _dev_long(item["semantic_mask"], dev).contiguous()
+        if tuple(sem.shape) != tuple(shape):
+            raise ValueError(f"semantic_mask is {tuple(sem.shape)}, the prediction {tuple(shape)}")
+        ignore, _ = ops.mask_eq(sem, 255)
+        stack = _stack_masks(masks, dev) if len(labels) else torch.zeros((0,) + tuple(shape), dtype=torch.uint8,
+                                                                         device=dev)
+        planes, overlap = [], 0
+        for cid in range(len(INSTANCE_CLASSES)):
+            ids = [j + 1 if l == cid else 0 for j, l in enumerate(labels)]
+            plane, over = ops.labels_from_stack(stack, ids, ignore)
+            planes.append(plane)
+            overlap += over
+        return torch.stack(planes), overlap
+
+    def evaluate_panoptic(self, dataloader, iou_percent=PANOPTIC_IOU_PERCENT, min_area: int = 3) -> Dict[str, float]:
+        """Panoptic Quality, AJI, object Dice, SEG and the F1 / average-precision sweep of the predicted instances
+        (predict_semantic_mask on the device, then semantic_to_instance_maps) against the items' instance_masks /
+        instance_labels, pixels whose semantic_mask is 255 ignored: metrics.panoptic_metrics_from_stats of the
+        statistics pooled over the loader (PANOPTIC_KEYS for the default thresholds), plus aji_image_mean (the mean
+        of the per-image AJI, both classes pooled, over the images that have a ground truth or a prediction: the
+        MoNuSeg convention) and gt_overlap_pixels (ground-truth pixels that more than one instance of a class
+        claims, where the id map keeps the later instance only).  Per image: one contingency table of the two class
+        planes (ops.label_pairs); no mask plane is expanded on the prediction side."""
+        self._label_map_models_only("evaluate_panoptic")
+        stats, image_aji, overlap = None, [], 0
+        for batch in dataloader:
+            for i, item in enumerate(batch["batch_items"]):
+                pred_ids, _, _ = self.semantic_to_instance_maps(self._predict_mask_device(batch["images"][i]), min_area)
+                gt_ids, over = self._gt_instance_maps(item, pred_ids.shape[1:], pred_ids.device)
+                overlap += over
+                st = instance_stats_from_pairs(ops.label_pairs(pred_ids, gt_ids), len(INSTANCE_CLASSES), iou_percent)
+                if int(st["n_pred"].sum()) + int(st["n_gt"].sum()) > 0:
+                    image_aji.append(int(st["aji_c"].sum()) / int(st["aji_u"].sum()))
+                stats = add_instance_stats(stats, st)
+        if stats is None:
+            raise ValueError("evaluate_panoptic: the loader holds no image")
+        result = panoptic_metrics_from_stats(stats, INSTANCE_CLASSES, iou_percent)
+        result["aji_image_mean"] = float(np.mean(image_aji)) if image_aji else float("nan")
+        result["gt_overlap_pixels"] = overlap
+        return result
+
+    def evaluate_by_size(self, dataloader, edges=SIZE_EDGES, class_names=CLASS_NAMES) -> Dict:
+        """visualization.py:1753-1817 (plot_size_based_performance) without the host round trip: for every class,
+        background included, the 4-connected components of the ground truth (ops.label_components(gt == c,
+        connectivity=4): scipy.ndimage.label's default) and, per object, the fraction of its pixels the prediction
+        gives the same class, binned by object area -> {"edges", "coverage": a list per bin [0, e0), [e0, e1), ...,
+        [e_last, inf) in the reference's order (image, class, object), "count", "mean" (NaN for an empty bin)}.
+        A 255 pixel belongs to no ground-truth object.  The component ids go through ops.label_pairs, whose ids end at
+        2^24 - 1: a class mask with more components than that (a noise mask beyond 4096 x 4096) raises ValueError."""
+        self._label_map_models_only("evaluate_by_size")
+        edges = tuple(int(e) for e in edges)
+        bins = [[] for _ in range(len(edges) + 1)]
+        for batch in dataloader:
+            for i, item in enumerate(batch["batch_items"]):
+                pred = self._predict_mask_device(batch["images"][i]).contiguous()
+                gt = _dev_long(item["semantic_mask"], pred.device).contiguous()
+                comps, same = [], []
+                for c in range(len(class_names)):
+                    labels, n, _ = ops.label_components(ops.mask_eq(gt, c)[0], connectivity=4)
+                    if n > ops.PAIRS_MAX_ID:
+                        raise ValueError(f"evaluate_by_size: the ground truth's class {c} has {n} components, the "
+                                         f"pair table's ids end at {ops.PAIRS_MAX_ID}")
+                    comps.append(labels)
+                    same.append(ops.mask_eq(pred, c)[0])
+                pairs = ops.label_pairs(torch.stack(comps), torch.stack(same).to(torch.int32))
+                for b, cov in zip(bins, size_strata_from_pairs(pairs, edges)):
+                    b.extend(cov)
+        return {"edges": edges, "coverage": bins, "count": [len(b) for b in bins],
+                "mean": [float(np.mean(b)) if b else float("nan") for b in bins]}
 
     # ---- train_eval.py:852-1021 ------------------------------------------------
     def evaluate(self, dataloader, coco_map: bool = False) -> Dict[str, float]:

@@ -40,6 +40,17 @@ numpy only, no sklearn.
 The contour metrics (Hausdorff distance, HD95, average symmetric surface distance, surface Dice, boundary F1,
 Boundary IoU) and the two lists of visualization.py:1687-1751 (plot_boundary_accuracy), from the integer
 statistics of ops.boundary_stats (boundary.hip), which rest on an exact distance transform on the device.
+
+    instance_stats_from_pairs(pairs, num_planes, iou_percent=(50, 55, ..., 95)) -> {name: array indexed by plane}
+    panoptic_metrics_from_stats(stats, class_names=("live", "dead"), iou_percent=...) -> {key: float}
+    calculate_panoptic_metrics(pred_ids, gt_ids, class_names=("live", "dead"), iou_percent=...) -> {key: float}
+    size_strata_from_pairs(pairs, edges=(100, 500, 1000, 5000)) -> [coverages per size bin]
+
+Instance metrics of two integer id maps (no reference counterpart; the size strata are
+visualization.py:1753-1817): Panoptic Quality (Kirillov et al. 2019), the Aggregated Jaccard Index (Kumar et al.
+2017), the object-level Dice of the GlaS contest (Sirinukunwattana et al. 2017), the SEG score of the Cell Tracking
+Challenge and the F1 / average-precision sweep over IoU 0.5 .. 0.95 (the 2018 Data Science Bowl's score), all from
+the sparse contingency table of ops.label_pairs (pairs.hip).  Every decision is taken in integers.
 """
 from __future__ import annotations
 
@@ -677,3 +688,221 @@ def calculate_viability_metrics(pred_live_count: int, pred_dead_count: int, gt_l
     return {"pred_viability": pred_viability, "gt_viability": gt_viability,
             "viability_accuracy": viability_accuracy, "pred_live_count": pred_live_count,
             "pred_dead_count": pred_dead_count, "gt_live_count": gt_live_count, "gt_dead_count": gt_dead_count}
+
+
+# ---- label-map instance metrics (the contingency table of ops.label_pairs) ---------------------------------
+PANOPTIC_IOU_PERCENT = tuple(range(50, 100, 5))
+INSTANCE_STAT_NAMES = ("n_pred", "n_gt", "tp50", "tp", "iou_sum", "aji_c", "aji_u", "objdice_g", "objdice_gw",
+                       "objdice_p", "objdice_pw", "seg_sum")
+
+
+def _iou_percent(iou_percent) -> Tuple[int, ...]:
+    import operator
+    try:
+        ts = tuple(operator.index(t) for t in iou_percent)
+    except TypeError:
+        raise ValueError(f"iou_percent must be a sequence of integers, got {iou_percent!r}") from None
+    if not ts or any(not 50 <= t <= 99 for t in ts):
+        raise ValueError(f"iou_percent must hold integers in 50..99 (above one half a match is unique), got "
+                         f"{iou_percent!r}")
+    return ts
+
+
+def _pair_rows(pairs) -> np.ndarray:
+    rows = np.asarray(pairs, dtype=np.int64).reshape(-1, 4)
+    if len(rows) and (rows.min() < 0 or (rows[:, 3] < 1).any()):
+        raise ValueError("pairs: rows are (plane, a, b, n) with ids >= 0 and n >= 1")
+    return rows
+
+
+def empty_instance_stats(num_planes: int, num_thresholds: int = len(PANOPTIC_IOU_PERCENT)) -> Dict[str, np.ndarray]:
+    """The statistics of nothing: what instance_stats_from_pairs results are added to."""
+    z = {k: np.zeros(num_planes, np.int64) for k in INSTANCE_STAT_NAMES}
+    z["tp"] = np.zeros((num_planes, num_thresholds), np.int64)
+    for k in ("iou_sum", "objdice_g", "objdice_p", "seg_sum"):
+        z[k] = np.zeros(num_planes, np.float64)
+    return z
+
+
+def instance_stats_from_pairs(pairs, num_planes: int, iou_percent: Sequence[int] = PANOPTIC_IOU_PERCENT
+                              ) -> Dict[str, np.ndarray]:
+    """pairs: the rows (plane, a, b, n) of ops.label_pairs(prediction ids, ground-truth ids), each plane one class ->
+    a dict of arrays indexed by plane that add over images with a plain + per entry.
+
+    With n(i, j) the table, area_a[i] = sum_b n(i, b) and area_b[j] = sum_a n(a, j) over the pixels that are not
+    ignored (column and row 0 included), and for i, j >= 1 U(i, j) = area_a[i] + area_b[j] - n(i, j):
+      n_pred, n_gt       objects (ids >= 1) on either side
+      tp [., T]          pairs with IoU > t / 100, decided as 100 n > t U, for t in iou_percent (50..99: unique)
+      tp50, iou_sum      the t = 50 matches and the float64 sum of their IoUs n / U in sorted (a, b) order
+      aji_c, aji_u       Kumar et al.: for each ground truth j in ascending order the prediction i* of largest IoU
+                         among those with n(i, j) > 0 (ranked by cross-multiplication, ties to the smallest i):
+                         C += n(i*, j), U += U(i*, j), i* used -- it may serve several ground truths; without an
+                         overlapping prediction U += area_b[j]; at the end U += area_a[i] of every unused prediction
+      objdice_g, _gw     GlaS: sum over the ground truths j, in id order, of area_b[j] * Dice(j, the prediction of
+                         largest n(i, j), ties to the smallest i; 0 without one) and the sum of area_b[j]; the term
+                         is the float64 nearest to the integer quotient 2 n area_b[j] / (area_a[i] + area_b[j])
+      objdice_p, _pw     the same from the predictions' side
+      seg_sum            sum over the ground truths of the IoU of the prediction with 2 n > area_b[j], if any
+    All products stay below 2^53 for planes of up to 8192 x 8192 pixels."""
+    ts = _iou_percent(iou_percent)
+    rows = _pair_rows(pairs)
+    if len(rows) and rows[:, 0].max() >= num_planes:
+        raise ValueError(f"pairs: plane {int(rows[:, 0].max())} of {num_planes}")
+    rows = rows[np.lexsort((rows[:, 2], rows[:, 1], rows[:, 0]))]
+    st = empty_instance_stats(num_planes, len(ts))
+    for q in range(num_planes):
+        r = rows[rows[:, 0] == q]
+        area_a: Dict[int, int] = {}
+        area_b: Dict[int, int] = {}
+        for _, i, j, n in r.tolist():
+            area_a[i] = area_a.get(i, 0) + n
+            area_b[j] = area_b.get(j, 0) + n
+        area_a.pop(0, None)
+        area_b.pop(0, None)
+        inner = [(i, j, n) for _, i, j, n in r.tolist() if i >= 1 and j >= 1]  # sorted by (a, b)
+        st["n_pred"][q], st["n_gt"][q] = len(area_a), len(area_b)
+        iou_sum, tp50, tp = 0.0, 0, [0] * len(ts)
+        best_g: Dict[int, Tuple[int, int, int]] = {}   # j -> (n, U, i) of the largest IoU
+        over_g: Dict[int, Tuple[int, int]] = {}        # j -> (n, i) of the largest overlap
+        over_p: Dict[int, Tuple[int, int]] = {}        # i -> (n, j)
+        seg_of: Dict[int, float] = {}
+        for i, j, n in inner:
+            u = area_a[i] + area_b[j] - n
+            if 100 * n > 50 * u:  # no threshold is below 50: nothing else can match
+                tp50 += 1
+                iou_sum += n / u
+                for k, t in enumerate(ts):
+                    if 100 * n > t * u:
+                        tp[k] += 1
+            b = best_g.get(j)
+            if b is None or n * b[1] > b[0] * u:  # i ascends within a j: strict keeps the smallest i of a tie
+                best_g[j] = (n, u, i)
+            if j not in over_g or n > over_g[j][0]:
+                over_g[j] = (n, i)
+            if i not in over_p or n > over_p[i][0]:  # j ascends within an i
+                over_p[i] = (n, j)
+            if 2 * n > area_b[j]:
+                seg_of[j] = n / u
+        st["iou_sum"][q], st["tp50"][q], st["tp"][q] = iou_sum, tp50, tp
+        c = u_sum = 0
+        used = set()
+        seg = dice_g = 0.0
+        for j in sorted(area_b):
+            b = best_g.get(j)
+            if b is None:
+                u_sum += area_b[j]
+            else:
+                c += b[0]
+                u_sum += b[1]
+                used.add(b[2])
+            seg += seg_of.get(j, 0.0)
+            if j in over_g:
+                n, i = over_g[j]
+                dice_g += 2 * n * area_b[j] / (area_a[i] + area_b[j])
+        dice_p = 0.0
+        for i in sorted(area_a):
+            if i not in used:
+                u_sum += area_a[i]
+            if i in over_p:
+                n, j = over_p[i]
+                dice_p += 2 * n * area_a[i] / (area_a[i] + area_b[j])
+        st["aji_c"][q], st["aji_u"][q] = c, u_sum
+        st["seg_sum"][q] = seg
+        st["objdice_g"][q], st["objdice_gw"][q] = dice_g, sum(area_b.values())
+        st["objdice_p"][q], st["objdice_pw"][q] = dice_p, sum(area_a.values())
+    return st
+
+
+def add_instance_stats(a: Optional[Dict[str, np.ndarray]], b: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """a + b entry by entry (a None: b)."""
+    return dict(b) if a is None else {k: a[k] + b[k] for k in INSTANCE_STAT_NAMES}
+
+
+def _panoptic_rows(st: Dict, ts: Sequence[int], suffix: str) -> Dict[str, float]:
+    """The scores of one row of statistics (scalars and tp [T])."""
+    tp, n_pred, n_gt = int(st["tp50"]), int(st["n_pred"]), int(st["n_gt"])
+    fp, fn = n_pred - tp, n_gt - tp
+    m = {
+        "pq": _ratio(st["iou_sum"], tp + 0.5 * fp + 0.5 * fn),
+        "sq": _ratio(st["iou_sum"], tp),
+        "dq": _ratio(tp, tp + 0.5 * fp + 0.5 * fn),
+        "aji": _ratio(int(st["aji_c"]), int(st["aji_u"])),
+        "objdice": 0.5 * (_ratio(st["objdice_g"], int(st["objdice_gw"])) +
+                          _ratio(st["objdice_p"], int(st["objdice_pw"]))),
+        "seg": _ratio(st["seg_sum"], n_gt),
+    }
+    scores = []
+    for k, t in enumerate(ts):
+        tpt = int(st["tp"][k])
+        m[f"f1_{t}"] = _ratio(2 * tpt, n_pred + n_gt)
+        scores.append(_ratio(tpt, n_pred + n_gt - tpt))  # TP / (TP + FP + FN)
+    m["ap_dsb"] = float(np.mean(scores))
+    return {f"{k}{suffix}": v for k, v in m.items()}
+
+
+def panoptic_keys(class_names: Sequence[str] = INSTANCE_CLASSES, iou_percent: Sequence[int] = PANOPTIC_IOU_PERCENT
+                  ) -> Tuple[str, ...]:
+    base = ["pq", "sq", "dq", "aji", "objdice", "seg"] + [f"f1_{t}" for t in iou_percent] + ["ap_dsb"]
+    return tuple(f"{k}_{c}" for c in class_names for k in base) + tuple(base) + ("mpq",)
+
+
+def panoptic_metrics_from_stats(stats: Dict[str, np.ndarray], class_names: Sequence[str] = INSTANCE_CLASSES,
+                                iou_percent: Sequence[int] = PANOPTIC_IOU_PERCENT) -> Dict[str, float]:
+    """The scores of (accumulated) instance_stats_from_pairs statistics, taken with the same iou_percent: per class c
+    pq_<c> = iou_sum / (TP + FP / 2 + FN / 2) at t = 50, sq_<c> = iou_sum / TP, dq_<c> = TP / (TP + FP / 2 + FN / 2),
+    aji_<c> = C / U, objdice_<c> = (objdice_g / objdice_gw + objdice_p / objdice_pw) / 2, seg_<c> = seg_sum / n_gt,
+    f1_<t>_<c> = 2 TP_t / (n_pred + n_gt) for every threshold and ap_dsb_<c> = the mean over the thresholds of
+    TP_t / (TP_t + FP_t + FN_t); the same pooled over the classes (their statistics added) without a suffix; mpq =
+    the mean of the class PQs over the classes with TP + FP + FN > 0.  An empty denominator gives NaN."""
+    ts = _iou_percent(iou_percent)
+    tp = np.asarray(stats["tp"])
+    if tp.ndim != 2 or tp.shape != (len(class_names), len(ts)):
+        raise ValueError(f"stats: tp is {tp.shape}, expected {len(class_names)} classes x {len(ts)} thresholds")
+    out: Dict[str, float] = {}
+    pqs = []
+    for q, name in enumerate(class_names):
+        row = {k: np.asarray(stats[k])[q] for k in INSTANCE_STAT_NAMES}
+        out.update(_panoptic_rows(row, ts, f"_{name}"))
+        if int(row["n_pred"]) + int(row["n_gt"]) - int(row["tp50"]) > 0:
+            pqs.append(out[f"pq_{name}"])
+    out.update(_panoptic_rows({k: np.asarray(stats[k]).sum(axis=0) for k in INSTANCE_STAT_NAMES}, ts, ""))
+    out["mpq"] = float(np.mean(pqs)) if pqs else float("nan")
+    return out
+
+
+def calculate_panoptic_metrics(pred_ids, gt_ids, class_names: Sequence[str] = INSTANCE_CLASSES,
+                               iou_percent: Sequence[int] = PANOPTIC_IOU_PERCENT) -> Dict[str, float]:
+    """pred_ids, gt_ids: device id maps [len(class_names), h, w] (or [h, w] for one class), int32 or int64, 0 the
+    background and a negative id an ignored pixel -> panoptic_metrics_from_stats of their contingency table."""
+    planes = 1 if pred_ids.dim() == 2 else int(pred_ids.shape[0])
+    if planes != len(class_names):
+        raise ValueError(f"calculate_panoptic_metrics: {planes} plane(s) for the classes {tuple(class_names)}")
+    stats = instance_stats_from_pairs(ops.label_pairs(pred_ids, gt_ids), planes, iou_percent)
+    return panoptic_metrics_from_stats(stats, class_names, iou_percent)
+
+
+SIZE_EDGES = (100, 500, 1000, 5000)  # visualization.py:1757
+
+
+def size_strata_from_pairs(pairs, edges: Sequence[int] = SIZE_EDGES) -> List[List[float]]:
+    """visualization.py:1762-1782 from a contingency table: pairs are the rows (plane, j, c, n) of
+    ops.label_pairs(ground-truth component ids, prediction == class as 0 / 1).  Every object j >= 1 has area(j) =
+    n(j, 0) + n(j, 1) and coverage n(j, 1) / area(j) (the float64 of the integer quotient: obj_pred.sum() /
+    obj_size); the coverages are placed by min <= area < max into the len(edges) + 1 bins [0, e0), [e0, e1), ...,
+    [e_last, inf), in (plane, id) order."""
+    edges = [int(e) for e in edges]
+    if any(b <= a for a, b in zip(edges, edges[1:])) or (edges and edges[0] <= 0):
+        raise ValueError(f"edges must be positive and ascending, got {edges!r}")
+    rows = _pair_rows(pairs)
+    if len(rows) and rows[:, 2].max() > 1:
+        raise ValueError("pairs: the second map must be 0 / 1")
+    rows = rows[np.lexsort((rows[:, 2], rows[:, 1], rows[:, 0]))]
+    bins: List[List[float]] = [[] for _ in range(len(edges) + 1)]
+    objs: Dict[Tuple[int, int], List[int]] = {}
+    for q, j, c, n in rows.tolist():
+        if j >= 1:
+            objs.setdefault((q, j), [0, 0])[c] += n  # dicts keep insertion order: (plane, id) ascending
+    for (q, j), (n0, n1) in objs.items():
+        area = n0 + n1
+        bins[int(np.searchsorted(edges, area, side="right"))].append(float(np.int64(n1) / np.int64(area)))
+    return bins

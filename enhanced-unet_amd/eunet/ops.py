@@ -1277,19 +1277,26 @@ def morph_u8(img, ksize: int, dilate: bool, iterations: int = 1):
     return out
 
 
-def label_components(img):
-    """8-connected components of a uint8 [h, w] image -> (labels int32 [h, w], n, areas int32 [n] on the device);
-    numbered 1..n in raster order of each component's first pixel.  Synchronises to read n."""
+def label_components(img, connectivity: int = 8):
+    """Connected components of a uint8 [h, w] image -> (labels int32 [h, w], n, areas int32 [n] on the device);
+    numbered 1..n in raster order of each component's first pixel.  connectivity 8 (skimage.measure.label's
+    connectivity=2) or 4 (scipy.ndimage.label's default).  Synchronises to read n."""
+    if connectivity not in (4, 8):
+        raise ValueError(f"label_components: connectivity must be 4 or 8, got {connectivity!r}")
     img = _u8(img)
     h, w = img.shape
     nbytes = c_size_t()
     call("eunet_label_workspace_bytes", h, w, ctypes.byref(nbytes))
-    cap = ((h + 1) // 2) * ((w + 1) // 2)
+    cap = ((h + 1) // 2) * ((w + 1) // 2) if connectivity == 8 else (h * w + 1) // 2
     labels = torch.empty(h, w, dtype=torch.int32, device=img.device)
     ws = torch.empty(nbytes.value // 4, dtype=torch.int32, device=img.device)
     areas = torch.empty(cap + 1, dtype=torch.int32, device=img.device)  # [cap] holds n
-    call("eunet_label_components", _ptr(img), h, w, _ptr(labels), _ptr(areas[cap:]), _ptr(areas), cap, _ptr(ws),
-         _stream())
+    if connectivity == 8:
+        call("eunet_label_components", _ptr(img), h, w, _ptr(labels), _ptr(areas[cap:]), _ptr(areas), cap, _ptr(ws),
+             _stream())
+    else:
+        call("eunet_label_components_conn", _ptr(img), h, w, _ptr(labels), _ptr(areas[cap:]), _ptr(areas), cap,
+             _ptr(ws), 4, _stream())
     n = int(areas[cap].item())
     return labels, n, areas[:n]
 
@@ -1518,6 +1525,114 @@ def watershed_split(labels, values, depth: float = 1.0, out=None):
     if single:
         return ids, counts, areas
     return ids, counts.view(n, nv), areas.view(n, nv, areas.shape[-1])
+
+
+# ---- label-map instance metrics (pairs.hip) -----------------------------------------------------
+PAIRS_FIRST_CAPACITY = 4096
+PAIRS_MAX_ID = _lib.PAIRS_MAX_ID  # the largest id of a map
+
+
+def _id_maps(name, what, t):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: {what} must be a tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: {what} must live on a GPU, got {t.device}")
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: {what} must be int32 or int64, got {t.dtype}")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"{name}: {what} must be [h, w] or [p, h, w], got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous")
+    return t
+
+
+def label_pairs(a, b, _table_capacity=None):
+    """The sparse contingency table of two label maps (include/eunet.h, "label-map instance metrics"): a and b are
+    [h, w] or [p, h, w] device tensors of equal shape, int32 or int64 each, contiguous -> numpy int64 [m, 4] of rows
+    (plane, a, b, n) sorted lexicographically: n pixels of the plane carry id a in the first map and id b in the
+    second.  Pixels that are background (0) in both maps are left out, pixels with a negative id in either are
+    ignored.  Ids reach 2^24 - 1; a larger one raises ValueError.  The table is read back: the call synchronises.
+    _table_capacity: the first size of the hash table (a power of two; it is doubled until every pair fits), for
+    tests."""
+    import numpy as np
+    name = "label_pairs"
+    a, b = _id_maps(name, "a", a), _id_maps(name, "b", b)
+    if a.shape != b.shape:
+        raise ValueError(f"{name}: the maps differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")
+    if a.device != b.device:
+        raise ValueError(f"{name}: the maps live on different devices: {a.device} vs {b.device}")
+    p, h, w = (1,) + tuple(a.shape) if a.dim() == 2 else tuple(a.shape)
+    if not (1 <= p <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE and p * h * w < 2 ** 31):
+        raise ValueError(f"{name}: maps {tuple(a.shape)} are outside p 1..65535, h and w 1..{_lib.EDT_MAX_SIDE}, "
+                         "p h w < 2^31")
+    if _table_capacity is None:
+        cap = PAIRS_FIRST_CAPACITY
+    else:
+        cap = int(_table_capacity)
+        if cap < 2 or cap > 2 ** 30 or cap & (cap - 1):
+            raise ValueError(f"{name}: _table_capacity must be a power of two in 2..2^30, got {_table_capacity!r}")
+    dev = a.device
+    nbytes = float(p * h * w * (a.element_size() + b.element_size()))
+    while True:
+        # one int64 buffer: the keys, then [cap] the invalid count, then the int32 counts and [cap] the overflow
+        buf = torch.empty(cap + 1 + (cap + 2) // 2, dtype=torch.int64, device=dev)
+        vals = buf[cap + 1:].view(torch.int32)
+        with kprof.timed("label_pairs", 0.0, nbytes):
+            call("eunet_label_pairs", _ptr(a), a.element_size(), _ptr(b), b.element_size(), p, h, w, _ptr(buf), _ptr(vals),
+                 cap, _ptr(vals[cap:]), _ptr(buf[cap:]), _stream())
+        host = buf.cpu().numpy()  # the one copy to the host
+        k, invalid = host[:cap], int(host[cap])
+        v = host[cap + 1:].view(np.int32)
+        if invalid:
+            raise ValueError(f"{name}: {invalid} pixel(s) hold an id above 2^24 - 1")
+        if v[cap] == 0:
+            break
+        if cap >= 2 ** 30:
+            raise _lib.EunetError(f"{name}: the pair table overflows at 2^30 slots")
+        cap *= 2  # nothing was dropped silently: the pass is run again with room for every pair
+    used = k != -1
+    k, n = k[used].view(np.uint64), v[:cap][used].astype(np.int64)  # unsigned: a plane above 32767 sets the top bit
+    order = np.argsort(k, kind="stable")  # plane, a, b are the key's fields from the top: key order is row order
+    k, n = k[order], n[order]
+    mask = np.uint64(_lib.PAIRS_MAX_ID)
+    fields = [k >> np.uint64(48), (k >> np.uint64(24)) & mask, k & mask]
+    return np.stack([f.astype(np.int64) for f in fields] + [n], axis=1).reshape(-1, 4)
+
+
+def labels_from_stack(masks, ids, ignore=None):
+    """masks uint8 (or bool) [n, h, w] on the device (non-zero = set), ids n integers (a sequence or an int32 device
+    tensor), ignore None or a uint8 / bool [h, w] device mask -> (labels int32 [h, w] on the device, overlap int):
+    labels[i] = ids[j] for the largest j with masks[j][i] set and ids[j] > 0, 0 where there is none, -1 where ignore
+    is set; overlap = the pixels that more than one selected plane claims.  n may be 0.  Synchronises to read
+    overlap."""
+    import numpy as np
+    name = "labels_from_stack"
+    if not isinstance(masks, torch.Tensor) or not masks.is_cuda or masks.dim() != 3 or \
+            masks.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"{name}: masks must be a uint8 or bool [n, h, w] device tensor")
+    masks = _u8(masks)
+    n, h, w = masks.shape
+    if not (0 <= n <= 65535 and h >= 1 and w >= 1 and h * w < 2 ** 31):
+        raise ValueError(f"{name}: masks {tuple(masks.shape)} are outside n 0..65535, h w < 2^31")
+    dev = masks.device
+    if isinstance(ids, torch.Tensor):
+        if ids.dtype != torch.int32 or ids.device != dev or tuple(ids.shape) != (n,):
+            raise ValueError(f"{name}: ids must be an int32 [{n}] tensor on {dev}")
+        ids_d = ids.contiguous()
+    else:
+        ids_h = _int_list(name, "ids", ids, -2 ** 31, 2 ** 31 - 1, n, n)
+        ids_d = upload(np.asarray(ids_h, np.int32), dev) if n else None
+    if ignore is not None:
+        if not isinstance(ignore, torch.Tensor) or ignore.device != dev or tuple(ignore.shape) != (h, w) or \
+                ignore.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"{name}: ignore must be a uint8 or bool [{h}, {w}] tensor on {dev}")
+        ignore = _u8(ignore)
+    out = torch.empty(h, w, dtype=torch.int32, device=dev)
+    overlap = torch.empty(1, dtype=torch.int64, device=dev)
+    with kprof.timed("labels_from_stack", 0.0, float(h * w * (n + 4 + (ignore is not None)))):
+        call("eunet_labels_from_stack", _ptr(masks) if n else None, n, h, w, _ptr(ids_d) if n else None,
+             None if ignore is None else _ptr(ignore), _ptr(out), _ptr(overlap), _stream())
+    return out, int(overlap.item())
 
 
 # ---- dual-branch fusion (fusion.hip) -------------------------------------------------

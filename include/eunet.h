@@ -458,7 +458,7 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
  * eunet_debug_status: synchronises the device; *count = failed checks since the last reset,
  * *unit_line = unit * 100000 + source line of the first (units: 1 capi, 2 conv3x3, 3 bn_pool_up,
  * 4 head, 5 instances, 6 baselines, 7 upconv, 8 bce_dice, 9 weightmap, 10 tiling, 11 warp,
- * 12 boundary, 13 watershed; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
+ * 12 boundary, 13 watershed, 14 pairs; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
 int eunet_debug_enabled(void);
 int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset);
 int eunet_debug_selftest(void* stream);
@@ -697,6 +697,32 @@ int eunet_watershed_saddles(const int32_t* dist, const int32_t* basin, int p, in
 int eunet_watershed_relabel(const int32_t* basin, int p, int h, int w, const int32_t* offs, const int32_t* table,
                             int nb_total, int32_t* ids, int32_t* areas, int amax, void* stream);
 
+/* ---- label-map instance metrics (pairs.hip) --------------------------------------
+ * No reference line: the reference scores instances through dense mask stacks (metrics.py:61-194).  Two integer id
+ * maps hold the same information, and every instance-level score of the pair (Panoptic Quality, the Aggregated
+ * Jaccard Index, object Dice, SEG, the F1 sweep over IoU; eunet/metrics.py, instance_stats_from_pairs) is a function
+ * of their sparse contingency table.
+ * eunet_label_pairs: a and b are p planes of h x w ids, each int32 or int64 independently (a_bytes / b_bytes 4 or
+ *   8).  For every pixel with a >= 0 and b >= 0 and not (a == 0 && b == 0) the count of the key (plane, a, b) grows
+ *   by one: background against background is counted nowhere, and a negative id on either side marks an ignored
+ *   pixel, counted nowhere.  An id above EUNET_PAIRS_MAX_ID on a pixel that is not ignored is counted in *invalid
+ *   (device int64) and nowhere else.  The table is an open-addressing hash table of `capacity` slots (a power of two
+ *   in 2..2^30): keys int64 [capacity] = plane << 48 | a << 24 | b, -1 where empty; counts int32 [capacity].  The
+ *   call clears the table, *overflow and *invalid first.  An insert that finds min(capacity, 64) successive slots
+ *   taken adds one to *overflow (device int32) and stores nothing: when *overflow != 0 the table is incomplete and
+ *   the call is repeated with a larger one.  Integer and order-free.  Limits: 1 <= h, w <= 8192, 1 <= p <= 65535,
+ *   p h w < 2^31.
+ * eunet_labels_from_stack: masks uint8 [n][h][w] (non-zero = set), ids int32 [n] on the device -> out int32 [h][w],
+ *   out[i] = ids[j] for the largest j with masks[j][i] != 0 and ids[j] > 0, 0 where there is none (later planes
+ *   overwrite earlier ones: eunet_rasterize_polygons' rule); where ignore (uint8 [h][w], may be null) is non-zero,
+ *   out[i] = -1.  *overlap (device int64, zeroed by the call) = the pixels claimed by more than one selected plane,
+ *   ignored pixels included.  n may be 0 (masks and ids are then not read).  n <= 65535, h w < 2^31. */
+#define EUNET_PAIRS_MAX_ID 16777215 /* 2^24 - 1 */
+int eunet_label_pairs(const void* a, int a_bytes, const void* b, int b_bytes, int p, int h, int w, int64_t* keys,
+                      int32_t* counts, long long capacity, int32_t* overflow, int64_t* invalid, void* stream);
+int eunet_labels_from_stack(const uint8_t* masks, int n, int h, int w, const int32_t* ids, const uint8_t* ignore,
+                            int32_t* out, int64_t* overlap, void* stream);
+
 /* ---- overlap-tile inference (tiling.hip) -------------------------------------
  * Prediction on an image larger than one forward pass (no reference line: the reference's only answer to a
  * large field of view is the resize down to max_size, dataset.py; overlap-tile prediction is the strategy
@@ -785,6 +811,11 @@ int eunet_morph_u8(const uint8_t* src, uint8_t* dst, uint8_t* tmp, int h, int w,
 int eunet_label_workspace_bytes(int h, int w, size_t* bytes);
 int eunet_label_components(const uint8_t* img, int h, int w, int32_t* labels, int32_t* n_out,
                            int32_t* areas, int areas_cap, int32_t* ws, void* stream);
+/* The same with the connectivity as an argument: 8 is eunet_label_components; 4 unites a pixel with its W and N
+ * neighbours only (scipy.ndimage.label's default structure, visualization.py:1753-1817), same numbering, and
+ * areas_cap >= ceil(h w / 2) (the checkerboard). */
+int eunet_label_components_conn(const uint8_t* img, int h, int w, int32_t* labels, int32_t* n_out,
+                                int32_t* areas, int areas_cap, int32_t* ws, int connectivity, void* stream);
 /* cv2.findContours(mask, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)[0][0] + cv2.arcLength(., True)
  * (train_eval.py:819-821) for every label k = 1..n of an int32 label map at once (Suzuki-Abe
  * outer-border following, 8-connectivity): stats int32 [n][8] = (axis-aligned chain steps,
