@@ -52,6 +52,7 @@ EDT_EQ, EDT_NE, EDT_EDGE = 0, 1, 2  # EUNET_EDT_*
 EDT_NONE = 2 ** 31 - 1
 EDT_MAX_VALUES, EDT_MAX_SIDE = 8, 8192
 BOUNDARY_MAX_CAP, BOUNDARY_MAX_RADII = 64, 8
+BOUNDARY_SOFTMAX, BOUNDARY_SIGMOID = 0, 1  # EUNET_BOUNDARY_*
 PAIRS_MAX_ID = 2 ** 24 - 1  # EUNET_PAIRS_MAX_ID
 
 
@@ -154,6 +155,11 @@ SIGNATURES = {
     "eunet_boundary_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],
     "eunet_boundary_stats": [_f, _f, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, _f, _f, _f, _f,
                              c_void_p],
+    "eunet_signed_distance_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],
+    "eunet_signed_distance": [_f, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _f, _f, c_void_p],
+    "eunet_boundary_loss_workspace_bytes": [c_int, c_int, c_int, POINTER(c_size_t)],
+    "eunet_boundary_loss_fwd": [_f, _f, c_int, c_int, c_int, c_int, c_int, POINTER(c_float * 3), _f, _f, _f, c_void_p],
+    "eunet_boundary_loss_bwd": [_f, _f, c_int, c_int, c_int, c_int, c_int, POINTER(c_float * 3), _f, _f, c_void_p],
     "eunet_tile_gather": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_tile_blend": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, _f, c_int,
                          c_int, c_int, _f, c_void_p],

@@ -19,6 +19,10 @@ bce_dice_loss / BCEDiceLoss are the sigmoid counterpart (csrc/bce_dice.hip): one
 + soft Dice, with K = 1 for foreground against background.  The reference has none (BASELINE.json's
 north star names it); include/eunet.h holds its definition.  It reports refused targets through the
 same counter and check_targets().
+
+boundary_loss / BoundaryLoss (csrc/sdf.hip) are the contour term: the softmax or sigmoid probability integrated
+against a signed distance map of the target (ops.signed_distance_map), after Kervadec et al. (MIDL 2019).  It sees
+no target, only the map, and is meant to be added to a region loss from the caller's own loop.
 """
 from __future__ import annotations
 
@@ -424,6 +428,93 @@ class BCEDiceLoss(nn.Module):
         return bce_dice_loss(logits, target, params=self.params(logits.shape[1]), pixel_weight=pixel_weight)
 
 
+# ---- boundary (surface) loss (csrc/sdf.hip; Kervadec et al., MIDL 2019; include/eunet.h holds the definition) ----
+def _check_boundary_args(logits, dist, activation, class_weight, what: str):
+    """The rules of boundary_loss that need no device, raised as ValueError; returns the K class weights."""
+    if activation not in ops.BOUNDARY_ACTIVATIONS:
+        raise ValueError(f"{what}: activation must be 'softmax' or 'sigmoid', not {activation!r}")
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
+        raise ValueError(f"{what}: expected [N, K, H, W] logits, got "
+                         f"{tuple(logits.shape) if isinstance(logits, torch.Tensor) else type(logits).__name__}")
+    if not logits.is_floating_point():
+        raise ValueError(f"{what}: logits must be floating point, got {logits.dtype}")
+    k = logits.shape[1]
+    if not 1 <= k <= 3:
+        raise ValueError(f"{what}: K must be 1..3, the logits have K = {k}")
+    if activation == "softmax" and k == 1:
+        raise ValueError(f"{what}: a softmax over K = 1 is constant; use activation='sigmoid'")
+    if not isinstance(dist, torch.Tensor):
+        raise ValueError(f"{what}: dist must be a tensor, got {type(dist).__name__}")
+    if dist.requires_grad:
+        raise ValueError(f"{what}: dist takes no gradient (requires_grad is set)")
+    if dist.dtype != torch.float32:
+        raise ValueError(f"{what}: dist must be float32, got {dist.dtype}")
+    if dist.shape != logits.shape:
+        raise ValueError(f"{what}: dist {tuple(dist.shape)} does not match logits {tuple(logits.shape)}")
+    if dist.device != logits.device:
+        raise ValueError(f"{what}: dist is on {dist.device}, the logits on {logits.device}")
+    if not dist.is_contiguous():
+        raise ValueError(f"{what}: dist must be contiguous")
+    if class_weight is not None and not isinstance(class_weight, (int, float, torch.Tensor)) and len(class_weight) < k:
+        raise ValueError(f"{what}: class_weight has {len(class_weight)} values for K = {k}")
+    return _triple(class_weight, 1.0, "class_weight")
+
+
+class BoundaryLossFunction(torch.autograd.Function):
+    """sum w_c p_c dist_c / (N H W Kw) with p the softmax or the sigmoid of the logits (eunet_boundary_loss_fwd);
+    the backward pass recomputes p and saves nothing but its inputs."""
+
+    @staticmethod
+    def forward(ctx, logits, dist, activation, cw):
+        logits = logits.contiguous().float()
+        if not logits.is_cuda:
+            raise _lib.EunetError("boundary_loss needs device tensors (no CPU fallback)")
+        n, k, h, w = logits.shape
+        dev = logits.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts = torch.empty(n, dtype=torch.float32, device=dev)
+        ws = torch.empty(ops.boundary_loss_workspace_bytes(n, h, w), dtype=torch.uint8, device=dev)
+        ops.boundary_loss_fwd(logits, dist, activation, cw[0], cw[1], cw[2], loss, parts, ws)
+        ctx.save_for_backward(logits, dist)
+        ctx.conf = (activation, cw)
+        ctx.mark_non_differentiable(parts)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, gloss, gparts):
+        logits, dist = ctx.saved_tensors
+        activation, cw = ctx.conf
+        glog = torch.empty_like(logits)
+        ops.boundary_loss_bwd(logits, dist, activation, cw[0], cw[1], cw[2], gloss.contiguous().float().reshape(1), glog)
+        return glog, None, None, None
+
+
+def boundary_loss(logits: torch.Tensor, dist: torch.Tensor, activation: str = "softmax", class_weight=None,
+                  return_parts: bool = False):
+    """The boundary loss: logits [N,K,H,W] (K = 2..3 for "softmax", 1..3 for "sigmoid", N <= 64), dist float32
+    [N,K,H,W] (ops.signed_distance_map of the target, or any prepared map; it takes no gradient) ->
+    sum_{n,c,x} w_c p_c(x) dist_c(x) / (N H W Kw), Kw = max(1, the number of non-zero class weights); parts [N] =
+    the same per sample, so the loss is their mean.  class_weight: None (all 1), a scalar, or K values --
+    (0, 1, 0) is the paper's idc = [1]."""
+    cw = _check_boundary_args(logits, dist, activation, class_weight, "boundary_loss")
+    loss, parts = BoundaryLossFunction.apply(logits, dist, ops.BOUNDARY_ACTIVATIONS[activation], tuple(cw))
+    return (loss, parts) if return_parts else loss
+
+
+class BoundaryLoss(nn.Module):
+    """weight * boundary_loss(logits, dist) with its configuration held as attributes: set them at any time (the
+    paper raises the weight over the epochs), the next call reads them."""
+
+    def __init__(self, activation: str = "softmax", class_weight=None, weight: float = 1.0):
+        super().__init__()
+        self.activation = activation
+        self.class_weight = class_weight
+        self.weight = weight
+
+    def forward(self, logits, dist):
+        return self.weight * boundary_loss(logits, dist, activation=self.activation, class_weight=self.class_weight)
+
+
 def _as_pixels(inputs: torch.Tensor, targets: torch.Tensor):
     """[N,K,*] logits / [N,*] targets -> [1,K,1,P] / [1,1,P] (pixel-mean losses only)."""
     if inputs.dim() < 2:
@@ -496,4 +587,4 @@ def tversky_loss(pred, target, num_classes: int = 3, alpha: float = 0.7):
 
 __all__ = ["combined_loss", "consistency_loss", "check_targets", "make_params", "reference_params", "FocalLoss",
            "CrossEntropyLoss", "dice_loss", "tversky_loss", "make_bce_dice_params", "BCEDiceFunction", "bce_dice_loss",
-           "BCEDiceLoss"]
+           "BCEDiceLoss", "BoundaryLossFunction", "boundary_loss", "BoundaryLoss"]

@@ -7,6 +7,7 @@ enqueued on torch's current HIP stream.  Activations are NHWC tensors
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 
@@ -1111,6 +1112,93 @@ def boundary_stats(pred, gt, num_classes: int = 3, ignore_index: int = 255, cap:
     ws = torch.empty(boundary_workspace_bytes(n, k, h, w) // 4, dtype=torch.int32, device=p.device)
     _boundary_stats_op(p, g, k, int(ignore_index), cap, radii, ws, surf, band if radii else None, refrows)
     return surf, band, refrows
+
+
+# ---- signed distance maps and the boundary loss (sdf.hip) ----------------------------------
+BOUNDARY_ACTIVATIONS = {"softmax": _lib.BOUNDARY_SOFTMAX, "sigmoid": _lib.BOUNDARY_SIGMOID}  # EUNET_BOUNDARY_*
+
+
+def signed_distance_workspace_bytes(n, k, h, w):
+    b = c_size_t()
+    call("eunet_signed_distance_workspace_bytes", n, k, h, w, ctypes.byref(b))
+    return b.value
+
+
+@_dispatched("T i i f f T! T!")
+def signed_distance(target, k, ignore_index, clip, scale, ws, out):
+    n, h, w = target.shape
+    # two transforms of k planes (distance_transform_sq's count), the combine pass (the target and two int32 planes in,
+    # one fp32 plane out) and, for k = 1, the foreground plane written and read by both transforms' column passes
+    nbytes = target.numel() * (2 * k * (8.0 + 4 * 4.0) + 8.0 + k * 12.0 + (8.0 if k == 1 else 0.0))
+    with kprof.timed("signed_distance", 0.0, nbytes):
+        call("eunet_signed_distance", _ptr(target), n, k, h, w, ignore_index, clip, scale, _ptr(ws), _ptr(out),
+             _stream())
+
+
+_signed_distance_op = signed_distance  # torch.ops.eunet.signed_distance writes into ws and out
+
+
+def signed_distance_map(target, num_classes: int, ignore_index=None, clip=None, scale: float = 1.0, out=None):
+    """target int64 [N,H,W] or [H,W] on the device -> float32 [N,K,H,W] (or [K,H,W]), K = num_classes in 1..3: per
+    class the signed Euclidean distance to the class contour, +sqrt(Dout) outside the class and -(sqrt(Din) - 1)
+    inside, 0 on a sample where the class or its complement is empty and on pixels equal to ignore_index (which
+    belong to no class), then scale * clamp(phi, -clip, clip) (include/eunet.h, eunet_signed_distance).  K = 1: the
+    class is target >= 1.  h, w <= 8192.  out: the buffer to write."""
+    name = "signed_distance_map"
+    if not isinstance(target, torch.Tensor):
+        raise ValueError(f"{name}: target must be a tensor")
+    if target.dtype != torch.int64:
+        raise ValueError(f"{name}: target must be int64, got {target.dtype}")
+    if target.dim() not in (2, 3):
+        raise ValueError(f"{name}: target must be [H, W] or [N, H, W], got {tuple(target.shape)}")
+    k = int(num_classes)
+    if not 1 <= k <= 3:
+        raise ValueError(f"{name}: num_classes must be 1..3, not {num_classes}")
+    if clip is not None and not (math.isfinite(float(clip)) and float(clip) > 0.0):
+        raise ValueError(f"{name}: clip must be None or a finite value > 0, got {clip}")
+    if not math.isfinite(float(scale)):
+        raise ValueError(f"{name}: scale must be finite, got {scale}")
+    ign = -(2 ** 31) if ignore_index is None else int(ignore_index)  # EUNET_NO_IGNORE
+    if not -2 ** 31 <= ign < 2 ** 31:
+        raise ValueError(f"{name}: ignore_index {ignore_index} is not an int32")
+    if k >= 2 and 0 <= ign < k:
+        raise ValueError(f"{name}: ignore_index {ign} is one of the {k} classes")
+    t, single = _int64_maps(name, "target", target)
+    n, h, w = t.shape
+    shape = (k, h, w) if single else (n, k, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=t.device)
+    else:
+        _out_buffer(name, "", out, shape, torch.float32, t.device)
+    ws = torch.empty(signed_distance_workspace_bytes(n, k, h, w) // 4, dtype=torch.int32, device=t.device)
+    _signed_distance_op(t, k, ign, 0.0 if clip is None else float(clip), float(scale), ws, out)
+    return out
+
+
+def boundary_loss_workspace_bytes(n, h, w):
+    b = c_size_t()
+    call("eunet_boundary_loss_workspace_bytes", n, h, w, ctypes.byref(b))
+    return b.value
+
+
+@_dispatched("T T i f f f T! T!? T!")
+def boundary_loss_fwd(logits, dist, activation, cw0, cw1, cw2, loss, parts, ws):
+    """torch.ops.eunet.boundary_loss_fwd: loss = sum w_c p_c dist_c / (N H W Kw), parts [N] per sample."""
+    n, k, h, w = logits.shape
+    cw = (_lib.c_float * 3)(cw0, cw1, cw2)
+    with kprof.timed("boundary_loss_fwd", 0.0, 8.0 * logits.numel()):
+        call("eunet_boundary_loss_fwd", _ptr(logits), _ptr(dist), n, k, h, w, activation, ctypes.byref(cw), _ptr(loss),
+             _ptr(parts), _ptr(ws), _stream())
+
+
+@_dispatched("T T i f f f T T!")
+def boundary_loss_bwd(logits, dist, activation, cw0, cw1, cw2, gloss, glogits):
+    """torch.ops.eunet.boundary_loss_bwd: glogits = gloss * d loss / d logits, one pass over logits and dist."""
+    n, k, h, w = logits.shape
+    cw = (_lib.c_float * 3)(cw0, cw1, cw2)
+    with kprof.timed("boundary_loss_bwd", 0.0, 12.0 * logits.numel()):
+        call("eunet_boundary_loss_bwd", _ptr(logits), _ptr(dist), n, k, h, w, activation, ctypes.byref(cw), _ptr(gloss),
+             _ptr(glogits), _stream())
 
 
 # ---- overlap-tile inference (tiling.hip; the geometry is eunet.tiling.TilePlan) ----------

@@ -458,7 +458,7 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
  * eunet_debug_status: synchronises the device; *count = failed checks since the last reset,
  * *unit_line = unit * 100000 + source line of the first (units: 1 capi, 2 conv3x3, 3 bn_pool_up,
  * 4 head, 5 instances, 6 baselines, 7 upconv, 8 bce_dice, 9 weightmap, 10 tiling, 11 warp,
- * 12 boundary, 13 watershed, 14 pairs; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
+ * 12 boundary, 13 watershed, 14 pairs, 15 sdf; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
 int eunet_debug_enabled(void);
 int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset);
 int eunet_debug_selftest(void* stream);
@@ -722,6 +722,60 @@ int eunet_label_pairs(const void* a, int a_bytes, const void* b, int b_bytes, in
                       int32_t* counts, long long capacity, int32_t* overflow, int64_t* invalid, void* stream);
 int eunet_labels_from_stack(const uint8_t* masks, int n, int h, int w, const int32_t* ids, const uint8_t* ignore,
                             int32_t* out, int64_t* overlap, void* stream);
+
+/* ---- signed distance maps and the boundary loss (sdf.hip) ---------------------------
+ * No reference line to cite: every loss of the reference is a region loss.  The boundary loss of Kervadec et al.,
+ * "Boundary loss for highly unbalanced segmentation" (MIDL 2019), integrates the class probability against the
+ * signed distance map of the ground truth; this comment is the definition of both.
+ *
+ * eunet_signed_distance: target int64 [N][H][W] -> out fp32 [N][K][H][W], K = 1..3.  Per sample n and class c the
+ * region is R = {x : target(x) = c}; for K = 1 the single class is "foreground", R = {x : target(x) >= 1}
+ * (EUNET_BCE_TARGET_FOREGROUND's rule; the call writes [target >= 1 and not ignored] to an int64 scratch plane of
+ * the workspace and transforms that).  With the exact int32 values of eunet_edt_sq,
+ *   Dout(x) = the squared distance to the nearest pixel of R         (EUNET_EDT_EQ)
+ *   Din(x)  = the squared distance to the nearest pixel not in R     (EUNET_EDT_NE)
+ *   phi_c(x) = +sqrt(Dout(x))        for x outside R
+ *   phi_c(x) = -(sqrt(Din(x)) - 1)   for x in R
+ * which is Kervadec's dist(neg) neg - (dist(pos) - 1) pos: a pixel of R that touches the complement has phi = 0,
+ * the first pixel outside has phi = +1.
+ *   Empty:  if R or its complement is empty in sample n, phi_c = 0 on the whole sample (there is no contour to pull
+ *           towards; EUNET_EDT_NONE never reaches a square root).
+ *   Ignore: a pixel equal to ignore_index (EUNET_NO_IGNORE = none) belongs to no class: it is outside every R and
+ *           is a site of every complement, and its own phi_c is 0 for every c, so it adds nothing to the loss.
+ *           The consequence: an ignored region acts as "not the class" and attracts the contour of an adjacent
+ *           region at distance 1 (a region pixel next to it has phi = 0, as next to any other class).  For K >= 2
+ *           ignore_index must not be one of 0 .. K-1 (EUNET_ERR_INVALID).  Any other value outside 0 .. K-1 is
+ *           simply of no class.
+ *   out = scale * clamp(phi, -clip, +clip); clip = 0 means no clamp, otherwise clip must be finite and > 0; scale
+ *           must be finite.  The square root, the clamp and the scaling are in fp64 from the exact integer, and the
+ *           result is rounded to fp32 once.
+ * ws (eunet_signed_distance_workspace_bytes): int32 [2][N][K][H][W], the EQ and the NE transform, followed for
+ * K = 1 by the int64 [N][H][W] foreground plane; 8-byte aligned.  One elementwise kernel after the two transforms
+ * reads both planes and the target and writes out, 16 bytes per lane when H W % 4 == 0 and the pointers are
+ * 16-byte aligned.  Limits are eunet_edt_sq's (h, w <= 8192, n <= 65535); no host synchronisation, no allocation. */
+int eunet_signed_distance_workspace_bytes(int n, int k, int h, int w, size_t* bytes);
+int eunet_signed_distance(const int64_t* target, int n, int k, int h, int w, int ignore_index, float clip,
+                          float scale, int32_t* ws, float* out, void* stream);
+/* eunet_boundary_loss_fwd: logits z and dist fp32 [N][K][H][W], K = 1..3, N <= 64.  dist is any map (the loss is
+ * linear in the probabilities): eunet_signed_distance's, clipped, normalised or otherwise prepared.
+ *   p = softmax over c of z (EUNET_BOUNDARY_SOFTMAX, K = 2, 3; K = 1 is EUNET_ERR_INVALID) or p_c = sigmoid(z_c)
+ *   (EUNET_BOUNDARY_SIGMOID, K = 1..3); w = class_weight, K host floats (null: all 1; Kervadec's idc = [1] is
+ *   (0, 1, 0)); Kw = max(1, #{c < K : w_c != 0}).
+ *   loss     = sum_{n,c,x} w_c p_c(x) dist_c(x) / (N H W Kw)
+ *   parts[n] = the same sum over sample n / (H W Kw)              (nullable; loss = the mean of parts)
+ * ws: eunet_boundary_loss_workspace_bytes (one float per sample and tile of 1024 pixels).  The partials are summed
+ * in fp64 in a fixed order: two runs are bit-identical.
+ * eunet_boundary_loss_bwd: glogits = (*gloss) d loss / d z (gloss: device scalar g), one pass, nothing saved:
+ *   softmax:  g p_j (w_j dist_j - sum_c w_c p_c dist_c) / (N H W Kw)
+ *   sigmoid:  g w_c dist_c p_c (1 - p_c) / (N H W Kw)
+ * The softmax is max-subtracted and the sigmoid pair comes from one exp, so logits of +-100 neither overflow nor
+ * cancel. */
+enum { EUNET_BOUNDARY_SOFTMAX = 0, EUNET_BOUNDARY_SIGMOID = 1 };
+int eunet_boundary_loss_workspace_bytes(int n, int h, int w, size_t* bytes);
+int eunet_boundary_loss_fwd(const float* logits, const float* dist, int n, int k, int h, int w, int activation,
+                            const float* class_weight, float* loss, float* parts, void* ws, void* stream);
+int eunet_boundary_loss_bwd(const float* logits, const float* dist, int n, int k, int h, int w, int activation,
+                            const float* class_weight, const float* gloss, float* glogits, void* stream);
 
 /* ---- overlap-tile inference (tiling.hip) -------------------------------------
  * Prediction on an image larger than one forward pass (no reference line: the reference's only answer to a
