@@ -41,6 +41,7 @@ int debug_read_boundary(unsigned*, unsigned*, bool);
 int debug_read_watershed(unsigned*, unsigned*, bool);
 int debug_read_pairs(unsigned*, unsigned*, bool);
 int debug_read_sdf(unsigned*, unsigned*, bool);
+int debug_read_cellprops(unsigned*, unsigned*, bool);
 #endif
 }  // namespace eunet
 
@@ -85,15 +86,15 @@ int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset) {
     eunet::set_error("debug_status: device synchronisation failed");
     return EUNET_ERR_HIP;
   }
-  int (*readers[15])(unsigned*, unsigned*, bool) = {eunet::debug_read_capi, eunet::debug_read_conv3x3,
+  int (*readers[16])(unsigned*, unsigned*, bool) = {eunet::debug_read_capi, eunet::debug_read_conv3x3,
                                                    eunet::debug_read_bnpool, eunet::debug_read_head,
                                                    eunet::debug_read_instances, eunet::debug_read_baselines,
                                                    eunet::debug_read_upconv, eunet::debug_read_bcedice,
                                                    eunet::debug_read_weightmap, eunet::debug_read_tiling,
                                                    eunet::debug_read_warp, eunet::debug_read_boundary,
                                                    eunet::debug_read_watershed, eunet::debug_read_pairs,
-                                                   eunet::debug_read_sdf};
-  for (int u = 0; u < 15; ++u) {
+                                                   eunet::debug_read_sdf, eunet::debug_read_cellprops};
+  for (int u = 0; u < 16; ++u) {
     unsigned line = 0, cnt = 0;
     const int rc = readers[u](&line, &cnt, reset != 0);
     if (rc != EUNET_OK) {

@@ -73,6 +73,12 @@ two integer id maps per class, and every score is a function of their sparse con
 builds on the device (ops.label_pairs, pairs.hip) and metrics.instance_stats_from_pairs reads in integers.  No
 mask plane per instance is expanded and no pair of masks is compared.
 
+Per-cell measurements (measure_cells, evaluate_measurements; no reference counterpart): the id maps of
+semantic_to_instance_maps go through one ops.cell_stats call (cellprops.hip), whose integer tables
+metrics.cell_measurements turns into area, centroid, axes, orientation, perimeter, circularity, holes and per-channel
+intensity of every cell; evaluate_measurements compares the areas and centroids of the predicted cells with those of
+the ground-truth cells they match at IoU > 1/2.
+
 Overlap-tile inference (no reference counterpart: the reference resizes every image down to max_size):
 Evaluator(..., tile=T) sends an image whose padded size exceeds T in either axis through the network tile by
 tile (eunet.tiling.plan; ops.tile_gather, forward_lowres on tile_batch tiles at a time, one ops.tile_blend
@@ -96,7 +102,8 @@ from .metrics import (CLASS_NAMES, INSTANCE_CLASSES, PANOPTIC_IOU_PERCENT, SIZE_
                       calculate_instance_metrics, calculate_iou, calculate_semantic_metrics,
                       calculate_viability_metrics, coco_image_matches, coco_map_from_matches, curve_edges,
                       curve_metrics_from_hist, instance_stats_from_pairs, panoptic_keys, panoptic_metrics_from_stats,
-                      size_strata_from_pairs)
+                      size_strata_from_pairs, AGREEMENT_KEYS, agreement_summary, cell_measurements,
+                      measurement_agreement)
 
 TTA_SCALES = (0.75, 1.25)
 
@@ -599,6 +606,61 @@ class Evaluator:
         result = panoptic_metrics_from_stats(stats, INSTANCE_CLASSES, iou_percent)
         result["aji_image_mean"] = float(np.mean(image_aji)) if image_aji else float("nan")
         result["gt_overlap_pixels"] = overlap
+        return result
+
+    # ---- per-cell measurements (no reference counterpart) ------------------------------------------------
+    def measure_cells(self, image: torch.Tensor, intensity=None, min_area: int = 3, pixel_size: float = 1.0) -> Dict:
+        """The measurements of every predicted cell of one image: the mask is predicted on the device
+        (predict_semantic_mask's), split into semantic_to_instance_maps' id maps, and one ops.cell_stats call on the
+        [2, h, w] ids gives the integer tables -> {"live": m, "dead": m, "n_live", "n_dead", "viability": n_live /
+        (n_live + n_dead), 0.0 without a cell}, m = metrics.cell_measurements' dict of the class plus "score", the
+        instance scores.  intensity: None (geometry only) or the caller's uint8 [h, w] / [h, w, c] image (c <= 3,
+        numpy or tensor) at the mask's size, whose per-cell mean_<ch>, std_<ch>, min_<ch>, max_<ch> are added."""
+        self._label_map_models_only("measure_cells")
+        ids, counts, scores = self.semantic_to_instance_maps(self._predict_mask_device(image), min_area)
+        if intensity is not None:
+            if not isinstance(intensity, torch.Tensor):
+                intensity = ops.upload(np.ascontiguousarray(intensity), ids.device)
+            elif not intensity.is_cuda:
+                intensity = intensity.to(ids.device)
+        stats = ops.cell_stats(ids, max(counts), intensity)
+        out: Dict = {}
+        for plane, name in enumerate(INSTANCE_CLASSES):
+            m = cell_measurements(stats, plane, pixel_size)
+            m = {k: v[:counts[plane]] for k, v in m.items()}  # the table has max(counts) rows for both classes
+            m["score"] = np.asarray(scores[plane], np.float64)
+            out[name] = m
+        n_live, n_dead = int(counts[0]), int(counts[1])
+        out.update(n_live=n_live, n_dead=n_dead, viability=n_live / (n_live + n_dead) if n_live + n_dead else 0.0)
+        return out
+
+    def evaluate_measurements(self, dataloader, min_area: int = 3) -> Dict[str, float]:
+        """How the measurements of the predicted cells agree with the ground truth's over the loader: per item the
+        predicted id maps (as evaluate_panoptic forms them) and _gt_instance_maps' go through ops.cell_stats each and
+        ops.label_pairs together; a predicted and a ground-truth cell are matched at IoU > 1 / 2
+        (metrics.measurement_agreement) -> metrics.AGREEMENT_KEYS per class, "<key>_live" and "<key>_dead":
+        n_matched, area_rel_err_mean, area_rel_err_median, area_bias, centroid_dist_mean (pixels), count_pred,
+        count_gt, mean_area_pred, mean_area_gt."""
+        self._label_map_models_only("evaluate_measurements")
+        parts = [[] for _ in INSTANCE_CLASSES]
+        seen = False
+        for batch in dataloader:
+            for i, item in enumerate(batch["batch_items"]):
+                seen = True
+                pred_ids, counts, _ = self.semantic_to_instance_maps(self._predict_mask_device(batch["images"][i]),
+                                                                     min_area)
+                gt_ids, _ = self._gt_instance_maps(item, pred_ids.shape[1:], pred_ids.device)
+                geom_pred = ops.cell_stats(pred_ids, max(counts))["geom"]
+                geom_gt = ops.cell_stats(gt_ids, len(item["instance_labels"]))["geom"]
+                pairs = ops.label_pairs(pred_ids, gt_ids)
+                for plane in range(len(INSTANCE_CLASSES)):
+                    parts[plane].append(measurement_agreement(pairs, geom_pred, geom_gt, plane))
+        if not seen:
+            raise ValueError("evaluate_measurements: the loader holds no image")
+        result = {}
+        for plane, name in enumerate(INSTANCE_CLASSES):
+            result.update({f"{k}_{name}": v for k, v in agreement_summary(parts[plane]).items()})
+        assert set(result) == {f"{k}_{c}" for k in AGREEMENT_KEYS for c in INSTANCE_CLASSES}
         return result
 
     def evaluate_by_size(self, dataloader, edges=SIZE_EDGES, class_names=CLASS_NAMES) -> Dict:

@@ -51,6 +51,14 @@ visualization.py:1753-1817): Panoptic Quality (Kirillov et al. 2019), the Aggreg
 2017), the object-level Dice of the GlaS contest (Sirinukunwattana et al. 2017), the SEG score of the Cell Tracking
 Challenge and the F1 / average-precision sweep over IoU 0.5 .. 0.95 (the 2018 Data Science Bowl's score), all from
 the sparse contingency table of ops.label_pairs (pairs.hip).  Every decision is taken in integers.
+
+    cell_measurements(stats, plane=0, pixel_size=1.0) -> {descriptor: float64 [n]}
+    population_summary(measurements, keys=...) -> {key: float}
+    measurement_agreement(pairs, geom_pred, geom_gt, plane) -> {...};  agreement_summary(parts) -> {key: float}
+
+Per-cell measurements (no reference counterpart): area, centroid, bounding box, second moments, axes, eccentricity,
+orientation, perimeters, circularity, Euler number, holes and per-channel intensity of every label, from the integer
+tables of ops.cell_stats (cellprops.hip), and how the measurements of matched predicted and ground-truth cells agree.
 """
 from __future__ import annotations
 
@@ -906,3 +914,164 @@ def size_strata_from_pairs(pairs, edges: Sequence[int] = SIZE_EDGES) -> List[Lis
         area = n0 + n1
         bins[int(np.searchsorted(edges, area, side="right"))].append(float(np.int64(n1) / np.int64(area)))
     return bins
+
+
+# ---- per-cell measurements (the integer tables of ops.cell_stats, cellprops.hip) ---------------------------
+MEASUREMENT_SUMMARY_KEYS = ("area", "equivalent_diameter", "major_axis", "minor_axis", "eccentricity", "circularity")
+AGREEMENT_KEYS = ("n_matched", "area_rel_err_mean", "area_rel_err_median", "area_bias", "centroid_dist_mean",
+                  "count_pred", "count_gt", "mean_area_pred", "mean_area_gt")
+
+
+def _int_ratios(num: Sequence[int], den: Sequence[int]) -> np.ndarray:
+    """num / den entry by entry, each the float64 nearest to the quotient of two Python integers of any size; NaN
+    where den is 0."""
+    return np.asarray([n / d if d else float("nan") for n, d in zip(num, den)], np.float64).reshape(len(num))
+
+
+def cell_measurements(stats: Dict, plane: int = 0, pixel_size: float = 1.0) -> Dict[str, np.ndarray]:
+    """The descriptors of the labels 1..n of one plane of ops.cell_stats' result (or of any dict with "geom" int64
+    [p, n + 1, 14], "shape" (h, w) and, optionally, "intensity" int64 [p, n + 1, c, 4]) -> {name: float64 [n]}, entry
+    i - 1 for label i.  A label with no pixel has area 0 and NaN everywhere else.  numpy only, float64.
+      area, centroid_x, centroid_y, bbox ([n, 4]: x0, y0, x1, y1 inclusive, in pixels whatever pixel_size is),
+      extent (area over the box's area), equivalent_diameter sqrt(4 A / pi)
+      mu20, mu02, mu11   the second central moments per pixel about the centroid, from pixel centres without the
+                         1 / 12 term of a pixel's own extent (regionprops' convention): (A sum x^2 - (sum x)^2) / A^2
+                         and so on, the numerator exact in Python integers (A sum x^2 passes 2^63 on a large cell)
+      major_axis, minor_axis   4 sqrt(l1), 4 sqrt(l2) of the eigenvalues l1 >= l2 of [[mu20, mu11], [mu11, mu02]]
+      eccentricity       sqrt(1 - l2 / l1), 0 where l1 = 0
+      orientation        atan2(2 mu11, mu20 - mu02) / 2: the angle of the major axis from the +x axis with y pointing
+                         down, in (-pi / 2, pi / 2]; 0 for an isotropic cell
+      perimeter_crack    q1 + q2 + q3 + 2 qd, the unit pixel edges between the label and anything else
+      perimeter          Gray's bit-quad estimate q2 + (q1 + q3 + 2 qd) / sqrt 2
+      circularity        4 pi A / perimeter^2, not clipped
+      euler_number       (q1 - q3 - 2 qd) / 4, 8-connected
+      holes              1 - euler_number: meaningful only where an id is one 8-connected component, which
+                         ops.label_components and the watershed both give
+      touches_border     1 where the box reaches the first or last row or column, else 0
+      mean_<ch>, std_<ch> (population), min_<ch>, max_<ch>   per channel ch = 0.. of the intensity table, if present
+    pixel_size s scales the lengths (centroid, diameter, axes, perimeters) by s and the areas (area, mu) by s^2."""
+    geom = np.asarray(stats["geom"])
+    if geom.ndim != 3 or geom.shape[2] != 14 or geom.dtype != np.int64:
+        raise ValueError(f"cell_measurements: geom must be int64 [p, n + 1, 14], got {geom.dtype} {geom.shape}")
+    if not 0 <= plane < geom.shape[0]:
+        raise ValueError(f"cell_measurements: plane {plane} of {geom.shape[0]}")
+    s = float(pixel_size)
+    if not (s > 0.0 and np.isfinite(s)):
+        raise ValueError(f"cell_measurements: pixel_size must be positive and finite, got {pixel_size!r}")
+    h, w = (int(v) for v in stats["shape"])
+    g = geom[plane, 1:]
+    n = len(g)
+    cols = [[int(v) for v in g[:, k]] for k in range(14)]  # Python integers: the products below are exact
+    A, sx, sy, sxx, syy, sxy = cols[:6]
+    present = g[:, 0] > 0
+    nan = np.where(present, 0.0, np.nan)  # added to what a label with no pixel must not report
+    area = g[:, 0].astype(np.float64)
+    A2 = [a * a for a in A]
+    mu20 = _int_ratios([a * q - m * m for a, q, m in zip(A, sxx, sx)], A2)
+    mu02 = _int_ratios([a * q - m * m for a, q, m in zip(A, syy, sy)], A2)
+    mu11 = _int_ratios([a * q - mx * my for a, q, mx, my in zip(A, sxy, sx, sy)], A2)
+    half, diff = (mu20 + mu02) / 2.0, (mu20 - mu02) / 2.0
+    root = np.sqrt(diff * diff + mu11 * mu11)
+    l1, l2 = half + root, np.maximum(half - root, 0.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ecc = np.where(l1 > 0.0, np.sqrt(np.maximum(1.0 - l2 / np.where(l1 > 0.0, l1, 1.0), 0.0)), 0.0) + nan
+        bbox = g[:, 6:10].astype(np.float64) + nan[:, None]
+        box_area = (bbox[:, 2] - bbox[:, 0] + 1.0) * (bbox[:, 3] - bbox[:, 1] + 1.0)
+        q1, q2, q3, qd = (g[:, k].astype(np.float64) for k in range(10, 14))
+        perimeter = q2 + (q1 + q3 + 2.0 * qd) / np.sqrt(2.0) + nan
+        euler = (q1 - q3 - 2.0 * qd) / 4.0 + nan
+        touches = ((g[:, 6] == 0) | (g[:, 7] == 0) | (g[:, 8] == w - 1) | (g[:, 9] == h - 1)).astype(np.float64) + nan
+        out = {
+            "area": area * s * s, "centroid_x": _int_ratios(sx, A) * s, "centroid_y": _int_ratios(sy, A) * s, "bbox": bbox,
+            "extent": area / box_area, "equivalent_diameter": np.sqrt(4.0 * area / np.pi) * s + nan,
+            "mu20": mu20 * s * s, "mu02": mu02 * s * s, "mu11": mu11 * s * s,
+            "major_axis": 4.0 * np.sqrt(l1) * s, "minor_axis": 4.0 * np.sqrt(l2) * s, "eccentricity": ecc,
+            "orientation": 0.5 * np.arctan2(2.0 * mu11, mu20 - mu02),
+            "perimeter_crack": (q1 + q2 + q3 + 2.0 * qd) * s + nan, "perimeter": perimeter * s,
+            "circularity": 4.0 * np.pi * area / (perimeter * perimeter), "euler_number": euler, "holes": 1.0 - euler,
+            "touches_border": touches,
+        }
+    inten = stats.get("intensity")
+    if inten is not None:
+        inten = np.asarray(inten)
+        if inten.ndim != 4 or inten.shape[:2] != geom.shape[:2] or inten.shape[3] != 4:
+            raise ValueError(f"cell_measurements: intensity must be [p, n + 1, c, 4], got {inten.shape}")
+        for ch in range(inten.shape[2]):
+            t = inten[plane, 1:, ch]
+            sv, sq = [int(v) for v in t[:, 0]], [int(v) for v in t[:, 1]]
+            out[f"mean_{ch}"] = _int_ratios(sv, A)
+            out[f"std_{ch}"] = np.sqrt(_int_ratios([max(a * q - v * v, 0) for a, q, v in zip(A, sq, sv)], A2))
+            out[f"min_{ch}"] = t[:, 2].astype(np.float64) + nan
+            out[f"max_{ch}"] = t[:, 3].astype(np.float64) + nan
+    assert all(len(v) == n for v in out.values())
+    return out
+
+
+def population_summary(measurements: Dict[str, np.ndarray], keys: Sequence[str] = MEASUREMENT_SUMMARY_KEYS
+                       ) -> Dict[str, float]:
+    """cell_measurements' dict -> {"count": the labels with area > 0, "<key>_mean", "<key>_median", "<key>_std"
+    (population) of every key in keys over those labels}; NaN where there is none."""
+    present = np.asarray(measurements["area"]) > 0
+    out = {"count": float(present.sum())}
+    for k in keys:
+        v = np.asarray(measurements[k], np.float64)
+        if v.ndim != 1:
+            raise ValueError(f"population_summary: {k} is not one number per label")
+        v = v[present]
+        for name, f in (("mean", np.mean), ("median", np.median), ("std", np.std)):
+            out[f"{k}_{name}"] = float(f(v)) if len(v) else float("nan")
+    return out
+
+
+def measurement_agreement(pairs, geom_pred, geom_gt, plane: int) -> Dict:
+    """How the measurements of one class plane's predicted cells agree with the ground truth's: pairs are the rows
+    (plane, a, b, n) of ops.label_pairs(prediction ids, ground-truth ids), geom_pred / geom_gt the "geom" tables of
+    ops.cell_stats of the two maps.  A predicted cell i and a ground-truth cell j are matched when 100 n > 50 U, U =
+    area_a[i] + area_b[j] - n with the areas of the pair table (instance_stats_from_pairs' integer predicate: IoU above
+    one half, hence unique) -> {"matches": int64 [m, 2] of (i, j) sorted, "area_rel": float64 [m] of (A_p - A_g) / A_g
+    with the areas of the geom tables, "centroid_dist": float64 [m] in pixels, "count_pred", "count_gt": the labels
+    with a pixel, "area_pred", "area_gt": their summed areas}.  agreement_summary pools a list of these."""
+    rows = _pair_rows(pairs)
+    gp, gg = np.asarray(geom_pred)[plane], np.asarray(geom_gt)[plane]
+    r = rows[rows[:, 0] == plane]
+    r = r[np.lexsort((r[:, 2], r[:, 1]))]
+    area_a: Dict[int, int] = {}
+    area_b: Dict[int, int] = {}
+    for _, i, j, n in r.tolist():
+        area_a[i] = area_a.get(i, 0) + n
+        area_b[j] = area_b.get(j, 0) + n
+    matches, rel, dist = [], [], []
+    for _, i, j, n in r.tolist():
+        if i < 1 or j < 1 or not 100 * n > 50 * (area_a[i] + area_b[j] - n):
+            continue
+        if i >= len(gp) or j >= len(gg):
+            raise ValueError(f"measurement_agreement: the pair ({i}, {j}) lies outside the tables")
+        ap, ag = int(gp[i, 0]), int(gg[j, 0])
+        matches.append((i, j))
+        rel.append((ap - ag) / ag)
+        dx = int(gp[i, 1]) / ap - int(gg[j, 1]) / ag
+        dy = int(gp[i, 2]) / ap - int(gg[j, 2]) / ag
+        dist.append(float(np.hypot(dx, dy)))
+    return {"matches": np.asarray(matches, np.int64).reshape(-1, 2), "area_rel": np.asarray(rel, np.float64),
+            "centroid_dist": np.asarray(dist, np.float64),
+            "count_pred": int((gp[1:, 0] > 0).sum()), "count_gt": int((gg[1:, 0] > 0).sum()),
+            "area_pred": int(gp[1:, 0].sum()), "area_gt": int(gg[1:, 0].sum())}
+
+
+def agreement_summary(parts: Sequence[Dict]) -> Dict[str, float]:
+    """measurement_agreement results of one class over several images, pooled -> AGREEMENT_KEYS: n_matched,
+    area_rel_err_mean / _median of |A_p - A_g| / A_g and area_bias, the mean of (A_p - A_g) / A_g, over the matched
+    pairs, centroid_dist_mean in pixels (NaN without a match), count_pred, count_gt, mean_area_pred, mean_area_gt (NaN
+    without a cell)."""
+    rel = np.concatenate([np.asarray(p["area_rel"], np.float64) for p in parts]) if parts else np.zeros(0)
+    dist = np.concatenate([np.asarray(p["centroid_dist"], np.float64) for p in parts]) if parts else np.zeros(0)
+    cp, cg = sum(p["count_pred"] for p in parts), sum(p["count_gt"] for p in parts)
+    nan = float("nan")
+    return {"n_matched": float(len(rel)),
+            "area_rel_err_mean": float(np.mean(np.abs(rel))) if len(rel) else nan,
+            "area_rel_err_median": float(np.median(np.abs(rel))) if len(rel) else nan,
+            "area_bias": float(np.mean(rel)) if len(rel) else nan,
+            "centroid_dist_mean": float(np.mean(dist)) if len(dist) else nan,
+            "count_pred": float(cp), "count_gt": float(cg),
+            "mean_area_pred": sum(p["area_pred"] for p in parts) / cp if cp else nan,
+            "mean_area_gt": sum(p["area_gt"] for p in parts) / cg if cg else nan}

@@ -1723,6 +1723,58 @@ def labels_from_stack(masks, ids, ignore=None):
     return out, int(overlap.item())
 
 
+# ---- per-cell measurements (cellprops.hip) -------------------------------------------------------
+CELL_GEOM_COLS = _lib.CELL_GEOM_COLS
+
+
+def cell_stats(ids, n: int, image=None):
+    """The integer sums of every label 1..n of a label map (include/eunet.h, "per-cell measurements"): ids [h, w] or
+    [p, h, w], int32 or int64, contiguous, on the device; image None or a contiguous uint8 [h, w] / [h, w, c] (c <= 3)
+    device tensor of the same device, shared by the planes -> {"geom": numpy int64 [p, n + 1, 14] (area, sum x, sum y,
+    sum x^2, sum y^2, sum x y, x0, y0, x1, y1, q1, q2, q3, qd; row 0 zero; a label with no pixel has the box w, h, -1,
+    -1), "intensity": numpy int64 [p, n + 1, c, 4] (sum, sum of squares, min, max per channel; 255 / 0 for a label
+    with no pixel) or None without an image, "skipped": numpy int64 [p], the pixels whose id is negative or above n
+    (measured nowhere), "shape": (h, w)}.  n may be 0.  The tables come back in one copy: the call synchronises.
+    metrics.cell_measurements forms the descriptors."""
+    import operator
+    name = "cell_stats"
+    ids = _id_maps(name, "ids", ids)
+    p, h, w = (1,) + tuple(ids.shape) if ids.dim() == 2 else tuple(ids.shape)
+    if not (1 <= p <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE):
+        raise ValueError(f"{name}: ids {tuple(ids.shape)} are outside p 1..65535, h and w 1..{_lib.EDT_MAX_SIDE}")
+    try:
+        n = operator.index(n)
+    except TypeError:
+        raise ValueError(f"{name}: n must be an integer, got {n!r}") from None
+    if not 0 <= n <= _lib.PAIRS_MAX_ID:
+        raise ValueError(f"{name}: n must lie in 0..{_lib.PAIRS_MAX_ID}, got {n}")
+    c = 0
+    if image is not None:
+        if not isinstance(image, torch.Tensor):
+            raise ValueError(f"{name}: image must be a tensor")
+        if image.dtype != torch.uint8:
+            raise ValueError(f"{name}: image must be uint8, got {image.dtype}")
+        if image.device != ids.device:
+            raise ValueError(f"{name}: image lives on {image.device}, the ids on {ids.device}")
+        if image.dim() not in (2, 3) or tuple(image.shape[:2]) != (h, w) or (image.dim() == 3 and
+                                                                              not 1 <= image.shape[2] <= 3):
+            raise ValueError(f"{name}: image must be [{h}, {w}] or [{h}, {w}, c] with c in 1..3, got "
+                             f"{tuple(image.shape)}")
+        if not image.is_contiguous():
+            raise ValueError(f"{name}: image must be contiguous")
+        c = 1 if image.dim() == 2 else int(image.shape[2])
+    rows = p * (n + 1)
+    cuts = (rows * CELL_GEOM_COLS, rows * (CELL_GEOM_COLS + 4 * c))
+    buf = torch.empty(cuts[1] + p, dtype=torch.int64, device=ids.device)  # geom, intensity, skipped: one copy back
+    with kprof.timed("cell_stats", 0.0, float(2 * p * h * w * ids.element_size() + p * h * w * c + 16 * buf.numel())):
+        call("eunet_cell_stats", _ptr(ids), ids.element_size(), p, h, w, n, None if image is None else _ptr(image), c,
+             _ptr(buf), _ptr(buf[cuts[0]:]) if c else None, _ptr(buf[cuts[1]:]), _stream())
+    host = buf.cpu().numpy()
+    return {"geom": host[:cuts[0]].reshape(p, n + 1, CELL_GEOM_COLS),
+            "intensity": host[cuts[0]:cuts[1]].reshape(p, n + 1, c, 4) if c else None,
+            "skipped": host[cuts[1]:], "shape": (h, w)}
+
+
 # ---- dual-branch fusion (fusion.hip) -------------------------------------------------
 def fusion_tiles(n, h, w):
     t, gt = c_int(), c_int()

@@ -723,6 +723,40 @@ int eunet_label_pairs(const void* a, int a_bytes, const void* b, int b_bytes, in
 int eunet_labels_from_stack(const uint8_t* masks, int n, int h, int w, const int32_t* ids, const uint8_t* ignore,
                             int32_t* out, int64_t* overlap, void* stream);
 
+/* ---- per-cell measurements (cellprops.hip) ------------------------------------------
+ * No reference line: the reference measures nothing per cell beyond the counts.  This comment is the definition.
+ * eunet_cell_stats: ids are p planes of h x w ids, int32 or int64 (elem_bytes 4 or 8); id 0 is background and the
+ *   ids 1..n are measured (0 <= n <= EUNET_PAIRS_MAX_ID).  A pixel whose id is negative or above n is counted in
+ *   skipped[plane] (device int64 [p], zeroed by the call), is measured nowhere and is "not this label" for its
+ *   neighbours.  With x the column and y the row index of a pixel:
+ *   geom int64 [p][n + 1][EUNET_CELL_GEOM_COLS], written entirely by the call (it need not be cleared); row 0 of a
+ *   plane stays zero; row i holds for the pixels of id i
+ *     0          area
+ *     1, 2       sum x, sum y
+ *     3, 4, 5    sum x^2, sum y^2, sum x y
+ *     6 .. 9     x0, y0, x1, y1 of the bounding box, inclusive; a label with no pixel has w, h, -1, -1
+ *     10 .. 13   the bit-quad counts q1, q2, q3, qd (Gray 1971): over all (h + 1) (w + 1) windows of 2 x 2 pixels
+ *                of the plane padded by one pixel of "outside", by how many of the window's four pixels carry the
+ *                label: exactly one -> q1, two that share an edge -> q2, the two on a diagonal -> qd, three -> q3
+ *                (four: not counted, the area covers them).  A window of up to four labels counts for each.
+ *   From these, on the host (eunet/metrics.py, cell_measurements): the crack perimeter q1 + q2 + q3 + 2 qd (unit
+ *   pixel edges between the label and anything else, the image border included), the Euler number (q1 - q3 - 2 qd)
+ *   / 4 for 8-connectivity and (q1 - q3 + 2 qd) / 4 for 4-connectivity, and Gray's perimeter estimate
+ *   q2 + (q1 + q3 + 2 qd) / sqrt 2.
+ *   image: null, or uint8 [h][w][c] (HWC, c = 1..3; c = 0 without an image) shared by all planes, of any byte
+ *   alignment (a lane reads its four pixels as dwords where they are 4-byte aligned and byte by byte otherwise);
+ *   inten int64 [p][n + 1][c][4], written entirely by the call: per channel sum v, sum v^2, min v, max v over the
+ *   label's pixels; a label with no pixel has min 255 and max 0; row 0 stays zero.  inten is not touched without
+ *   an image.
+ *   Every value is an integer below 2^63 (sum x^2 <= 8191^2 2^26) formed with 64-bit integer atomics, the bounding
+ *   box and the intensity range with signed atomic min / max on the values themselves: the tables do not depend on
+ *   the order of evaluation.  One pass over the ids and the image (a run of one id within 256 pixels of a row adds
+ *   its sums once, in closed form) and one pass over the windows (only windows that are not of one value add).
+ *   Limits: 1 <= h, w <= EUNET_EDT_MAX_SIDE, 1 <= p <= 65535.  No host synchronisation, no allocation. */
+#define EUNET_CELL_GEOM_COLS 14
+int eunet_cell_stats(const void* ids, int elem_bytes, int p, int h, int w, int n, const uint8_t* image, int c,
+                     int64_t* geom, int64_t* inten, int64_t* skipped, void* stream);
+
 /* ---- signed distance maps and the boundary loss (sdf.hip) ---------------------------
  * No reference line to cite: every loss of the reference is a region loss.  The boundary loss of Kervadec et al.,
  * "Boundary loss for highly unbalanced segmentation" (MIDL 2019), integrates the class probability against the
