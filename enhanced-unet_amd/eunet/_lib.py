@@ -55,6 +55,8 @@ BOUNDARY_MAX_CAP, BOUNDARY_MAX_RADII = 64, 8
 BOUNDARY_SOFTMAX, BOUNDARY_SIGMOID = 0, 1  # EUNET_BOUNDARY_*
 PAIRS_MAX_ID = 2 ** 24 - 1  # EUNET_PAIRS_MAX_ID
 CELL_GEOM_COLS = 14  # EUNET_CELL_GEOM_COLS
+CELL_HULL_COLS = 11  # EUNET_CELL_HULL_COLS
+CELL_HULL_MAX_ROWS = 2 ** 28  # EUNET_CELL_HULL_MAX_ROWS
 
 
 class OptTensor(ctypes.Structure):
@@ -180,6 +182,7 @@ SIGNATURES = {
     "eunet_label_pairs": [_f, c_int, _f, c_int, c_int, c_int, c_int, _f, _f, ctypes.c_longlong, _f, _f, c_void_p],
     "eunet_labels_from_stack": [_f, c_int, c_int, c_int, _f, _f, _f, _f, c_void_p],
     "eunet_cell_stats": [_f, c_int, c_int, c_int, c_int, c_int, _f, c_int, _f, _f, _f, c_void_p],
+    "eunet_cell_hulls": [_f, c_int, c_int, c_int, c_int, c_int, _f, _f, _f, _f, _f, _f, c_void_p],
     "eunet_outer_perimeter": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
     "eunet_mask_eq": [_f, c_int, c_int64, c_int64, _f, _f, c_void_p],
     "eunet_mask_and": [_f, _f, c_int64, _f, _f, c_void_p],

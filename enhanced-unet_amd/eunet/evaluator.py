@@ -103,7 +103,7 @@ from .metrics import (CLASS_NAMES, INSTANCE_CLASSES, PANOPTIC_IOU_PERCENT, SIZE_
                       calculate_viability_metrics, coco_image_matches, coco_map_from_matches, curve_edges,
                       curve_metrics_from_hist, instance_stats_from_pairs, panoptic_keys, panoptic_metrics_from_stats,
                       size_strata_from_pairs, AGREEMENT_KEYS, agreement_summary, cell_measurements,
-                      measurement_agreement)
+                      hull_measurements, measurement_agreement)
 
 TTA_SCALES = (0.75, 1.25)
 
@@ -609,13 +609,16 @@ class Evaluator:
         return result
 
     # ---- per-cell measurements (no reference counterpart) ------------------------------------------------
-    def measure_cells(self, image: torch.Tensor, intensity=None, min_area: int = 3, pixel_size: float = 1.0) -> Dict:
+    def measure_cells(self, image: torch.Tensor, intensity=None, min_area: int = 3, pixel_size: float = 1.0,
+                      hull: bool = False) -> Dict:
         """The measurements of every predicted cell of one image: the mask is predicted on the device
         (predict_semantic_mask's), split into semantic_to_instance_maps' id maps, and one ops.cell_stats call on the
         [2, h, w] ids gives the integer tables -> {"live": m, "dead": m, "n_live", "n_dead", "viability": n_live /
         (n_live + n_dead), 0.0 without a cell}, m = metrics.cell_measurements' dict of the class plus "score", the
         instance scores.  intensity: None (geometry only) or the caller's uint8 [h, w] / [h, w, c] image (c <= 3,
-        numpy or tensor) at the mask's size, whose per-cell mean_<ch>, std_<ch>, min_<ch>, max_<ch> are added."""
+        numpy or tensor) at the mask's size, whose per-cell mean_<ch>, std_<ch>, min_<ch>, max_<ch> are added.
+        hull=True adds metrics.hull_measurements' keys (convex area, solidity, the Feret diameters, ...) from one
+        ops.cell_hulls call on the same ids."""
         self._label_map_models_only("measure_cells")
         ids, counts, scores = self.semantic_to_instance_maps(self._predict_mask_device(image), min_area)
         if intensity is not None:
@@ -624,9 +627,12 @@ class Evaluator:
             elif not intensity.is_cuda:
                 intensity = intensity.to(ids.device)
         stats = ops.cell_stats(ids, max(counts), intensity)
+        hulls = ops.cell_hulls(ids, stats) if hull else None
         out: Dict = {}
         for plane, name in enumerate(INSTANCE_CLASSES):
             m = cell_measurements(stats, plane, pixel_size)
+            if hulls is not None:
+                m.update(hull_measurements(hulls, stats, plane, pixel_size))
             m = {k: v[:counts[plane]] for k, v in m.items()}  # the table has max(counts) rows for both classes
             m["score"] = np.asarray(scores[plane], np.float64)
             out[name] = m

@@ -1007,6 +1007,65 @@ def cell_measurements(stats: Dict, plane: int = 0, pixel_size: float = 1.0) -> D
     return out
 
 
+HULL_KEYS = ("convex_area", "solidity", "convex_perimeter", "convexity", "feret_max", "feret_max_angle", "feret_min",
+             "feret_min_angle", "feret_ratio", "hull_vertices")
+
+
+def _fold_angle(dy: np.ndarray, dx: np.ndarray) -> np.ndarray:
+    """The direction of (dx, dy) as the angle of a line: atan2 folded into (-pi / 2, pi / 2]."""
+    a = np.arctan2(dy, dx)
+    return np.where(a > np.pi / 2, a - np.pi, np.where(a <= -np.pi / 2, a + np.pi, a))
+
+
+def hull_measurements(hulls: Dict, stats: Dict, plane: int = 0, pixel_size: float = 1.0) -> Dict[str, np.ndarray]:
+    """The convex-hull descriptors of the labels 1..n of one plane: hulls is ops.cell_hulls' result (or any dict with
+    "hull" int64 [p, n + 1, 11]), stats the ops.cell_stats result it was formed from ("geom" int64 [p, n + 1, 14]) ->
+    {name: float64 [n]}, entry i - 1 for label i, NaN everywhere for a label with no pixel.  The hull is that of the
+    pixel squares (include/eunet.h, "per-cell convex hulls").  numpy only, float64.
+      convex_area        the hull's area, column 1 / 2
+      solidity           area / convex area = 2 A / column 1, the quotient of two Python integers; in (0, 1]
+      convex_perimeter   column 2 / 2^16
+      convexity          convex_perimeter / perimeter_crack (cell_measurements'), in (0, 1]
+      feret_max          the largest distance between two hull vertices, sqrt(column 3)
+      feret_max_angle    the direction of that pair from the +x axis with y pointing down, in (-pi / 2, pi / 2]
+      feret_min          the smallest width between two parallel lines that hold the hull, one of them along a hull
+                         edge: column 8 / sqrt(column 9^2 + column 10^2)
+      feret_min_angle    the direction the width is measured in, across that edge, in (-pi / 2, pi / 2]
+      feret_ratio        feret_min / feret_max, in (0, 1]
+      hull_vertices      column 0
+    pixel_size s scales the lengths (perimeter, Feret diameters) by s and convex_area by s^2."""
+    hull, geom = np.asarray(hulls["hull"]), np.asarray(stats["geom"])
+    if hull.ndim != 3 or hull.shape[2] != 11 or hull.dtype != np.int64:
+        raise ValueError(f"hull_measurements: hull must be int64 [p, n + 1, 11], got {hull.dtype} {hull.shape}")
+    if geom.ndim != 3 or geom.shape[2] != 14 or geom.dtype != np.int64 or geom.shape[:2] != hull.shape[:2]:
+        raise ValueError(f"hull_measurements: geom must be int64 {hull.shape[:2] + (14,)}, got {geom.dtype} {geom.shape}")
+    if not 0 <= plane < hull.shape[0]:
+        raise ValueError(f"hull_measurements: plane {plane} of {hull.shape[0]}")
+    s = float(pixel_size)
+    if not (s > 0.0 and np.isfinite(s)):
+        raise ValueError(f"hull_measurements: pixel_size must be positive and finite, got {pixel_size!r}")
+    t, g = hull[plane, 1:], geom[plane, 1:]
+    if ((t[:, 0] > 0) != (g[:, 0] > 0)).any():
+        raise ValueError("hull_measurements: the hulls and the stats disagree on which labels have a pixel")
+    nan = np.where(t[:, 0] > 0, 0.0, np.nan)  # added to what a label with no pixel must not report
+    f = t.astype(np.float64)  # every column is below 2^53
+    crack = (g[:, 10] + g[:, 11] + g[:, 12] + 2 * g[:, 13]).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        per = f[:, 2] / 65536.0 + nan
+        fmax = np.sqrt(f[:, 3]) + nan
+        fmin = f[:, 8] / np.sqrt(f[:, 9] * f[:, 9] + f[:, 10] * f[:, 10])
+        out = {
+            "convex_area": f[:, 1] / 2.0 * s * s + nan,
+            "solidity": _int_ratios([2 * int(a) for a in g[:, 0]], [int(v) for v in t[:, 1]]),
+            "convex_perimeter": per * s, "convexity": per / crack,
+            "feret_max": fmax * s, "feret_max_angle": _fold_angle(f[:, 7] - f[:, 5], f[:, 6] - f[:, 4]) + nan,
+            "feret_min": fmin * s, "feret_min_angle": _fold_angle(f[:, 9], -f[:, 10]) + nan,
+            "feret_ratio": fmin / fmax, "hull_vertices": f[:, 0] + nan,
+        }
+    assert tuple(out) == HULL_KEYS and all(len(v) == len(t) for v in out.values())
+    return out
+
+
 def population_summary(measurements: Dict[str, np.ndarray], keys: Sequence[str] = MEASUREMENT_SUMMARY_KEYS
                        ) -> Dict[str, float]:
     """cell_measurements' dict -> {"count": the labels with area > 0, "<key>_mean", "<key>_median", "<key>_std"

@@ -1775,6 +1775,73 @@ def cell_stats(ids, n: int, image=None):
             "skipped": host[cuts[1]:], "shape": (h, w)}
 
 
+# ---- per-cell convex hulls (hull.hip) --------------------------------------------------------------
+CELL_HULL_COLS = _lib.CELL_HULL_COLS
+
+
+def cell_hulls(ids, stats):
+    """The convex hull of every label 1..n of a label map (include/eunet.h, "per-cell convex hulls"): ids as for
+    cell_stats, stats the dict cell_stats(ids, n, ...) returned for the same ids (n = geom.shape[1] - 1; its bounding
+    boxes give the row layout) -> {"hull": numpy int64 [p, n + 1, 11] (vertex count, twice the hull's area, the
+    perimeter in 2^-16 pixels, the largest squared vertex distance and its pair xa, ya, xb, yb, the minimum width's
+    numerator c and its edge dx, dy; all zero for a label with no pixel), "verts": per plane a list of n int32
+    [nv_i, 2] arrays of (x, y), label i at index i - 1, in the header's order, "ext": numpy int32 [R, 2], per label and
+    row of its box the smallest and largest x, (w, -1) for a row without a pixel, "row_off": numpy int64
+    [p (n + 1) + 1], the first row of every label in ext, "shape": (h, w)}.  Stats that do not belong to these ids
+    raise ValueError: nothing is stored outside the tables.  The tables come back in one copy: the call synchronises.
+    metrics.hull_measurements forms the descriptors."""
+    import numpy as np
+    name = "cell_hulls"
+    ids = _id_maps(name, "ids", ids)
+    p, h, w = (1,) + tuple(ids.shape) if ids.dim() == 2 else tuple(ids.shape)
+    if not (1 <= p <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE):
+        raise ValueError(f"{name}: ids {tuple(ids.shape)} are outside p 1..65535, h and w 1..{_lib.EDT_MAX_SIDE}")
+    if not isinstance(stats, dict) or "geom" not in stats or "shape" not in stats:
+        raise ValueError(f"{name}: stats must be cell_stats' dict (\"geom\", \"shape\")")
+    if tuple(int(v) for v in stats["shape"]) != (h, w):
+        raise ValueError(f"{name}: the stats are of a {tuple(stats['shape'])} map, the ids are {(h, w)}")
+    geom = np.asarray(stats["geom"])
+    if geom.dtype != np.int64 or geom.ndim != 3 or geom.shape[0] != p or geom.shape[1] < 1 or \
+            geom.shape[2] != CELL_GEOM_COLS:
+        raise ValueError(f"{name}: geom must be int64 [{p}, n + 1, {CELL_GEOM_COLS}], got {geom.dtype} {geom.shape}")
+    n = geom.shape[1] - 1
+    if n > _lib.PAIRS_MAX_ID:
+        raise ValueError(f"{name}: n must lie in 0..{_lib.PAIRS_MAX_ID}, got {n}")
+    L = p * (n + 1)
+    y0, y1 = geom[:, :, 7].reshape(L), geom[:, :, 9].reshape(L)
+    rows = np.where(np.arange(L) % (n + 1) == 0, 0, np.maximum(y1 - y0 + 1, 0))  # id 0 has no rows
+    present = rows > 0
+    if (present & ((y0 < 0) | (y1 >= h))).any():
+        raise ValueError(f"{name}: a bounding box of the stats leaves the {h} rows of the map")
+    row_off = np.zeros(L + 1, np.int64)
+    np.cumsum(rows, out=row_off[1:])
+    R = int(row_off[L])
+    if R > _lib.CELL_HULL_MAX_ROWS:
+        raise ValueError(f"{name}: the labels' boxes have {R} rows together, above 2^28")
+    layout = np.zeros(L + 1 + (L + 1) // 2, np.int64)  # row_off, then row_y0 as int32: one upload
+    layout[:L + 1] = row_off
+    layout[L + 1:].view(np.int32)[:L] = np.where(present, y0, 0)
+    layout_d = upload(layout, ids.device)
+    cuts = np.cumsum([L * CELL_HULL_COLS, p, 2 * (R + L), R]).tolist()  # hull, outside, verts, ext in int64 words
+    buf = torch.empty(cuts[3], dtype=torch.int64, device=ids.device)
+    with kprof.timed(name, 0.0, float(p * h * w * ids.element_size() + 8 * buf.numel() + 8 * layout.size)):
+        call("eunet_cell_hulls", _ptr(ids), ids.element_size(), p, h, w, n, _ptr(layout_d), _ptr(layout_d[L + 1:]),
+             _ptr(buf[cuts[2]:]) if R else _ptr(buf), _ptr(buf[cuts[1]:]), _ptr(buf), _ptr(buf[cuts[0]:]), _stream())
+    host = buf.cpu().numpy()  # the one copy to the host
+    outside = host[cuts[0]:cuts[1]]
+    if outside.any():
+        raise ValueError(f"{name}: {int(outside.sum())} pixel(s) lie outside their label's rows: the stats are not "
+                         "of these ids")
+    hull = host[:cuts[0]].reshape(p, n + 1, CELL_HULL_COLS)
+    slots = host[cuts[1]:cuts[2]].view(np.int32).reshape(-1, 2)
+    start = 2 * (row_off[:L] + np.arange(L))
+    nv = hull[:, :, 0].reshape(L)
+    verts = [[slots[start[q * (n + 1) + i]:start[q * (n + 1) + i] + nv[q * (n + 1) + i]] for i in range(1, n + 1)]
+             for q in range(p)]
+    return {"hull": hull, "verts": verts, "ext": host[cuts[2]:].view(np.int32).reshape(R, 2), "row_off": row_off,
+            "shape": (h, w)}
+
+
 # ---- dual-branch fusion (fusion.hip) -------------------------------------------------
 def fusion_tiles(n, h, w):
     t, gt = c_int(), c_int()

@@ -757,6 +757,52 @@ int eunet_labels_from_stack(const uint8_t* masks, int n, int h, int w, const int
 int eunet_cell_stats(const void* ids, int elem_bytes, int p, int h, int w, int n, const uint8_t* image, int c,
                      int64_t* geom, int64_t* inten, int64_t* skipped, void* stream);
 
+/* ---- per-cell convex hulls (hull.hip) -------------------------------------------------
+ * No reference line: the reference measures nothing per cell.  This comment is the definition.
+ * eunet_cell_hulls: ids, elem_bytes, p, h, w, n as for eunet_cell_stats; ids 0, negative ids and ids above n are not
+ *   measured.  The point set of label i is the four corner lattice points (x, y), (x + 1, y), (x, y + 1),
+ *   (x + 1, y + 1) of every pixel (column x, row y) carrying id i: the hull is that of the pixel SQUARES, so its area
+ *   is >= the label's area and the solidity area / convex area lies in (0, 1], 1 for a rectangle.
+ *   The hull is strictly convex: no vertex lies on the segment between its neighbours.  The vertices are listed from
+ *   the corner with the smallest y, then the smallest x, along the top edge first: top edge left to right, right chain
+ *   downwards, bottom edge right to left, left chain upwards.  With y pointing down this makes the shoelace sum
+ *   sum_k (x_k y_{k+1} - x_{k+1} y_k) positive; the unit pixel gives (0,0), (1,0), (1,1), (0,1) and the sum 2.  A label
+ *   with a pixel has at least 4 vertices and at most 2 (rows + 1), rows = y1 - y0 + 1 of its bounding box.
+ *   The caller gives the row layout, which it has from eunet_cell_stats' bounding boxes (eunet/ops.py, cell_hulls):
+ *   with L = p (n + 1) and r = plane (n + 1) + id the flat index of a label, row_off int64 [L + 1] (device) is the
+ *   exclusive cumulative sum of the labels' row counts (0 for id 0 and for a label with no pixel), R = row_off[L] <=
+ *   EUNET_CELL_HULL_MAX_ROWS, and row_y0 int32 [L] (device) the image row of a label's first row.
+ *   Every entry of the four outputs is written by the call; a label with no pixel has all zeros.
+ *   ext int32 [R][2]: row row_off[r] + (y - row_y0[r]) holds the smallest and the largest x of label r in image row y;
+ *     a row of the label's box where it has no pixel holds (w, -1).
+ *   verts int32 [2 (R + L)][2]: the hull vertices (x, y) of label r start at slot 2 (row_off[r] + r), of which the
+ *     label owns 2 (rows + 1); slots past the label's vertex count are zero.
+ *   hull int64 [p][n + 1][EUNET_CELL_HULL_COLS]:
+ *     0        the number of hull vertices
+ *     1        twice the hull's area (the shoelace sum)
+ *     2        sum over the edges of floor(2^16 sqrt((double)(dx^2 + dy^2))): the hull's perimeter in 2^-16 pixels, the
+ *              fp64 square root taken from the exact integer
+ *     3        the largest squared distance between two hull vertices (the maximum Feret diameter squared)
+ *     4 .. 7   xa, ya, xb, yb of the vertex pair (i < j) attaining it; among equals the lexicographically smallest
+ *              (i, j) in vertex order
+ *     8        c: per hull edge e = (v_k -> v_{k+1}), c_e = the maximum over all vertices v of cross(v_{k+1} - v_k,
+ *              v - v_k), an integer >= 0; column 8 is the c_e of the edge with the smallest c_e^2 / |e|^2 (compared
+ *              exactly, in 128-bit products: c_e^2 |e'|^2 reaches 2^81), the smallest k among equals
+ *     9, 10    dx, dy of that edge; the minimum Feret diameter is c / sqrt(dx^2 + dy^2), measured across the edge
+ *   outside int64 [p]: the measured pixels whose row falls outside [row_y0[r], row_y0[r] + rows) of their label, or
+ *     whose label's slice does not lie inside 0..R in order.  They are stored nowhere: when outside is not all zero the
+ *     layout is not this map's and the tables mean nothing.  No store leaves the tables whatever the layout holds.
+ *   One pass over the ids (a run of one id within 256 pixels of a row issues one 32-bit atomic min and one atomic max)
+ *   and one wave per label: Andrew's monotone chain over the row extents, which are sorted by y already, then the
+ *   vertex pairs and edge x vertex pairs shared by the 64 lanes.  Every value is an integer and does not depend on the
+ *   order of evaluation.  Limits as eunet_cell_stats; pointers 8-byte aligned (row_y0 4).  No host synchronisation, no
+ *   allocation. */
+#define EUNET_CELL_HULL_COLS 11
+#define EUNET_CELL_HULL_MAX_ROWS 268435456 /* 2^28 */
+int eunet_cell_hulls(const void* ids, int elem_bytes, int p, int h, int w, int n, const int64_t* row_off,
+                     const int32_t* row_y0, int32_t* ext, int32_t* verts, int64_t* hull, int64_t* outside,
+                     void* stream);
+
 /* ---- signed distance maps and the boundary loss (sdf.hip) ---------------------------
  * No reference line to cite: every loss of the reference is a region loss.  The boundary loss of Kervadec et al.,
  * "Boundary loss for highly unbalanced segmentation" (MIDL 2019), integrates the class probability against the
