@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "labelmap.h"
 
 EUNET_DEBUG_UNIT(boundary)
 
@@ -158,25 +159,6 @@ __global__ __launch_bounds__(ROW_NT) void edt_rows_kernel(int32_t* out, int w) {
   }
 }
 
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // floor(2^16 sqrt(d2)) = the integer square root of N = d2 2^32 (d2 < 2^28, so N < 2^60 is exact in a double and
 // the rounded double root is within 1 of it)
 __device__ __forceinline__ unsigned long long isqrt_q16(unsigned d2) {
@@ -240,7 +222,7 @@ __global__ __launch_bounds__(NT) void refrows_kernel(const int64_t* pred, const 
   }
 #pragma unroll
   for (int i = 0; i < 18; ++i) {
-    const unsigned s = wave_sum_u32(cnt[i]);
+    const unsigned s = wave_sum(cnt[i]);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(&tot[i], s);
   }
   __syncthreads();
@@ -312,9 +294,9 @@ __global__ __launch_bounds__(NT) void boundary_stats_kernel(const int64_t* pred,
   const bool lead = (threadIdx.x & 63) == 0;
 #pragma unroll
   for (int dir = 0; dir < 2; ++dir) {
-    const unsigned z = wave_sum_u32(zero[dir]), ov = wave_sum_u32(over[dir]), no = wave_sum_u32(none[dir]);
-    const unsigned m = wave_max_u32(big[dir]);
-    const unsigned long long s = wave_sum_u64(sum[dir]);
+    const unsigned z = wave_sum(zero[dir]), ov = wave_sum(over[dir]), no = wave_sum(none[dir]);
+    const unsigned m = wave_max(big[dir]);
+    const unsigned long long s = wave_sum(sum[dir]);
     if (lead) {
       if (z) atomicAdd(&hist[dir * nb], z);
       if (ov) atomicAdd(&hist[dir * nb + cap2 + 1], ov);
@@ -328,7 +310,7 @@ __global__ __launch_bounds__(NT) void boundary_stats_kernel(const int64_t* pred,
     if (j < nr) {
 #pragma unroll
       for (int e = 0; e < 3; ++e) {
-        const unsigned s = wave_sum_u32(bc[j][e]);
+        const unsigned s = wave_sum(bc[j][e]);
         if (lead && s) atomicAdd(&bandc[j * 3 + e], s);
       }
     }
@@ -347,10 +329,6 @@ __global__ __launch_bounds__(NT) void boundary_stats_kernel(const int64_t* pred,
   }
   if ((int)threadIdx.x < 3 * nr && bandc[threadIdx.x])
     atomicAdd(band + (long long)c * nr * 3 + threadIdx.x, (unsigned long long)bandc[threadIdx.x]);
-}
-
-bool shape_ok(int n, int h, int w) {
-  return n >= 1 && n <= 65535 && h >= 1 && h <= EUNET_EDT_MAX_SIDE && w >= 1 && w <= EUNET_EDT_MAX_SIDE;
 }
 
 // both passes of one transform; gate / ign: the ignore rule (gate null: none)
@@ -381,7 +359,7 @@ extern "C" {
 int eunet_edt_sq(const int64_t* labels, int n, int h, int w, const int64_t* values, int nv, int mode, int32_t* out,
                  void* stream) {
   EUNET_REQUIRE(labels && values && out, "edt_sq: null pointer");
-  EUNET_REQUIRE(shape_ok(n, h, w), "edt_sq: bad shape (n 1..65535, h and w 1..%d)", EUNET_EDT_MAX_SIDE);
+  EUNET_REQUIRE(plane_stack_ok(n, h, w, false), "edt_sq: bad shape (n 1..65535, h and w 1..%d)", EUNET_EDT_MAX_SIDE);
   EUNET_REQUIRE(nv >= 1 && nv <= EUNET_EDT_MAX_VALUES, "edt_sq: 1..%d values", EUNET_EDT_MAX_VALUES);
   EUNET_REQUIRE(mode == EUNET_EDT_EQ || mode == EUNET_EDT_NE || mode == EUNET_EDT_EDGE, "edt_sq: unknown mode %d", mode);
   EUNET_REQUIRE(((uintptr_t)labels & 7u) == 0 && ((uintptr_t)out & 3u) == 0, "edt_sq: misaligned labels / out");
@@ -394,8 +372,8 @@ int eunet_edt_sq(const int64_t* labels, int n, int h, int w, const int64_t* valu
 
 int eunet_boundary_workspace_bytes(int n, int k, int h, int w, size_t* bytes) {
   EUNET_REQUIRE(bytes, "boundary_workspace_bytes: null pointer");
-  EUNET_REQUIRE(shape_ok(n, h, w) && k >= 1 && k <= 3, "boundary_workspace_bytes: bad shape (k 1..3, h and w 1..%d)",
-                EUNET_EDT_MAX_SIDE);
+  EUNET_REQUIRE(plane_stack_ok(n, h, w, false) && k >= 1 && k <= 3,
+                "boundary_workspace_bytes: bad shape (k 1..3, h and w 1..%d)", EUNET_EDT_MAX_SIDE);
   *bytes = (size_t)2 * n * k * h * w * sizeof(int32_t);
   return EUNET_OK;
 }
@@ -404,8 +382,8 @@ int eunet_boundary_stats(const int64_t* pred, const int64_t* gt, int n, int h, i
                          const int* radii, int nr, int32_t* ws, int64_t* surf, int64_t* band, int64_t* refrows,
                          void* stream) {
   EUNET_REQUIRE(pred && gt && ws && surf && refrows, "boundary_stats: null pointer");
-  EUNET_REQUIRE(shape_ok(n, h, w) && k >= 1 && k <= 3, "boundary_stats: bad shape (n 1..65535, k 1..3, h and w 1..%d)",
-                EUNET_EDT_MAX_SIDE);
+  EUNET_REQUIRE(plane_stack_ok(n, h, w, false) && k >= 1 && k <= 3,
+                "boundary_stats: bad shape (n 1..65535, k 1..3, h and w 1..%d)", EUNET_EDT_MAX_SIDE);
   EUNET_REQUIRE(cap >= 1 && cap <= EUNET_BOUNDARY_MAX_CAP, "boundary_stats: cap 1..%d", EUNET_BOUNDARY_MAX_CAP);
   EUNET_REQUIRE(nr >= 0 && nr <= EUNET_BOUNDARY_MAX_RADII && (nr == 0 || (radii && band)),
                 "boundary_stats: 0..%d radii (with their array and band)", EUNET_BOUNDARY_MAX_RADII);

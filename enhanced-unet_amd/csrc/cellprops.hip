@@ -12,12 +12,15 @@
 // -1 is a plain signed value; nothing is stored shifted and no pass follows).  Every loop is bounded by the shapes or
 // by a constant, every result is an integer and independent of the order in which the atomics land.
 #include "common.h"
+#include "labelmap.h"
 
 EUNET_DEBUG_UNIT(cellprops)
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == LM_NT, "labelmap.h sizes blocks of NT");
+constexpr int GRID_CAP = 4096;  // blocks of a grid-stride launch
 constexpr int PV = 4;             // pixels a lane holds
 constexpr int WAVE_PX = 64 * PV;  // pixels a wave holds
 constexpr int GC = EUNET_CELL_GEOM_COLS;
@@ -130,8 +133,7 @@ __global__ __launch_bounds__(NT) void cell_moments_kernel(const T* __restrict__ 
       }
     }
     // skipped pixels of the chunk: one add per wave
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) skip += __shfl_xor(skip, o, 64);
+    skip = wave_sum(skip);
     if (lane == 0 && skip) {
       EUNET_DASSERT(plane >= 0 && plane < p);
       add64(skipped + plane, (long long)skip);
@@ -296,39 +298,33 @@ __global__ __launch_bounds__(NT) void cell_quads_kernel(const T* __restrict__ id
   }
 }
 
-unsigned grid_for(long long threads, long long cap = 4096) {
-  long long b = (threads + NT - 1) / NT;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
 template <typename T>
 void launch_cells(const void* ids, int p, int h, int w, const uint8_t* image, int c, const Tables& t,
                   int64_t* skipped, hipStream_t s) {
   const long long rows_px = (long long)p * h * ((w + WAVE_PX - 1) / WAVE_PX);
-  const unsigned gm = grid_for(rows_px * 64);
+  const unsigned gm = grid_for(rows_px * 64, GRID_CAP);
   const T* src = (const T*)ids;
   long long* sk = (long long*)skipped;
   switch (c) {
     case 0:
-      cell_init_kernel<0><<<grid_for(t.rows * GC), NT, 0, s>>>(t, h, w);
+      cell_init_kernel<0><<<grid_for(t.rows * GC, GRID_CAP), NT, 0, s>>>(t, h, w);
       cell_moments_kernel<T, 0><<<gm, NT, 0, s>>>(src, p, h, w, image, t, sk);
       break;
     case 1:
-      cell_init_kernel<1><<<grid_for(t.rows * (GC + 4)), NT, 0, s>>>(t, h, w);
+      cell_init_kernel<1><<<grid_for(t.rows * (GC + 4), GRID_CAP), NT, 0, s>>>(t, h, w);
       cell_moments_kernel<T, 1><<<gm, NT, 0, s>>>(src, p, h, w, image, t, sk);
       break;
     case 2:
-      cell_init_kernel<2><<<grid_for(t.rows * (GC + 8)), NT, 0, s>>>(t, h, w);
+      cell_init_kernel<2><<<grid_for(t.rows * (GC + 8), GRID_CAP), NT, 0, s>>>(t, h, w);
       cell_moments_kernel<T, 2><<<gm, NT, 0, s>>>(src, p, h, w, image, t, sk);
       break;
     default:
-      cell_init_kernel<3><<<grid_for(t.rows * (GC + 12)), NT, 0, s>>>(t, h, w);
+      cell_init_kernel<3><<<grid_for(t.rows * (GC + 12), GRID_CAP), NT, 0, s>>>(t, h, w);
       cell_moments_kernel<T, 3><<<gm, NT, 0, s>>>(src, p, h, w, image, t, sk);
       break;
   }
   const long long rows_win = (long long)p * (h + 1) * ((w + 1 + 63) / 64);
-  cell_quads_kernel<T><<<grid_for(rows_win * 64), NT, 0, s>>>(src, p, h, w, t);
+  cell_quads_kernel<T><<<grid_for(rows_win * 64, GRID_CAP), NT, 0, s>>>(src, p, h, w, t);
 }
 
 }  // namespace
@@ -339,7 +335,7 @@ int eunet_cell_stats(const void* ids, int elem_bytes, int p, int h, int w, int n
                      int64_t* geom, int64_t* inten, int64_t* skipped, void* stream) {
   EUNET_REQUIRE(ids && geom && skipped, "cell_stats: null pointer");
   EUNET_REQUIRE(elem_bytes == 4 || elem_bytes == 8, "cell_stats: int32 or int64 ids (elem_bytes 4 or 8)");
-  EUNET_REQUIRE(p >= 1 && p <= 65535 && h >= 1 && h <= EUNET_EDT_MAX_SIDE && w >= 1 && w <= EUNET_EDT_MAX_SIDE,
+  EUNET_REQUIRE(plane_stack_ok(p, h, w, false),
                 "cell_stats: bad shape (p 1..65535, h and w 1..%d)", EUNET_EDT_MAX_SIDE);
   EUNET_REQUIRE(n >= 0 && n <= EUNET_PAIRS_MAX_ID, "cell_stats: n must lie in 0..%d (got %d)", EUNET_PAIRS_MAX_ID, n);
   EUNET_REQUIRE(image ? (c >= 1 && c <= 3 && inten) : c == 0,
@@ -348,10 +344,7 @@ int eunet_cell_stats(const void* ids, int elem_bytes, int p, int h, int w, int n
                     ((uintptr_t)ids & (uintptr_t)(elem_bytes - 1)) == 0,
                 "cell_stats: misaligned pointer");
   const hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(skipped, 0, sizeof(int64_t) * (size_t)p, s) != hipSuccess) {
-    eunet::set_error("cell_stats: memset failed");
-    return EUNET_ERR_HIP;
-  }
+  if (!fill_async(skipped, 0, sizeof(int64_t) * (size_t)p, s, "cell_stats")) return EUNET_ERR_HIP;
   const Tables t = {(long long*)geom, image ? (long long*)inten : nullptr, (long long)p * (n + 1), n};
   if (elem_bytes == 4) launch_cells<int32_t>(ids, p, h, w, image, c, t, skipped, s);
   else launch_cells<int64_t>(ids, p, h, w, image, c, t, skipped, s);

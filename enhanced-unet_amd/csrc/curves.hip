@@ -7,6 +7,7 @@
 // order-free, so the histogram of a whole validation set is the sum of its images' and every curve follows
 // from it on the host (eunet/metrics.py).  The contract is in include/eunet.h (eunet_score_hist).
 #include "common.h"
+#include "labelmap.h"
 
 namespace {
 
@@ -47,13 +48,6 @@ __device__ __forceinline__ void add_item(const Hist& h, int key, unsigned count,
   if (q) atomicAdd(&h.conf[key >> 1], (unsigned long long)q);
 }
 
-// sum over the wave of v (each <= 2^26: four pixels of at most 2^24), exact in 64 bits
-__device__ __forceinline__ unsigned long long wave_sum_u(unsigned v) {
-#pragma unroll
-  for (int o = 1; o < 32; o <<= 1) v += __shfl_xor(v, o, 64);  // 32 lanes: <= 2^31
-  return (unsigned long long)v + (unsigned long long)__shfl_xor(v, 32, 64);
-}
-
 // Every lane brings one item of `count` pixels (the same count on every lane; key < 0: none).  Saturated maps
 // put the whole wave on one (bin, truth) address: the lanes that share the first pending lane's key are
 // counted with a ballot and added once, at most twice in a row (background next to one cell class); what is
@@ -69,7 +63,7 @@ __device__ __forceinline__ void wave_add(const Hist& h, int key, unsigned count,
     const bool mate = key == lk;  // lk >= 0, so a lane without an item is never a mate
     const unsigned long long mates = __ballot(mate);
     if (__popcll(mates) < MIN_MATES) break;
-    const unsigned long long qs = wave_sum_u(mate ? q : 0u);
+    const unsigned long long qs = wave_sum_wide(mate ? q : 0u);  // each <= 2^26: four pixels of at most 2^24
     if (lane == lead) {
       atomicAdd(&h.cnt[lk], count * (unsigned)__popcll(mates));
       if (qs) atomicAdd(&h.conf[lk >> 1], qs);
@@ -168,8 +162,7 @@ __global__ __launch_bounds__(NT) void score_hist_kernel(const float* probs, cons
     if (pos) atomicAdd(out + 3 * b + 1, (unsigned long long)pos);
     if (cf) atomicAdd(out + 3 * b + 2, cf);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ninv += __shfl_xor(ninv, o, 64);
+  ninv = wave_sum(ninv);
   if ((threadIdx.x & 63) == 0 && ninv) atomicAdd(invalid, (unsigned long long)ninv);
 }
 

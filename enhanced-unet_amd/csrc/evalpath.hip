@@ -7,6 +7,7 @@
 // All of it is HBM-bound integer / per-pixel work: one pass per op, 16-byte or
 // 8-byte lanes, block-level integer reductions (exact, order-free).
 #include "common.h"
+#include "labelmap.h"
 
 namespace {
 
@@ -35,9 +36,7 @@ __global__ __launch_bounds__(NT) void semantic_counts_kernel(const int64_t* pred
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
-    unsigned int v = c[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const unsigned int v = wave_sum(c[i]);
     if (lane == 0) red[wv][i] = v;
   }
   __syncthreads();
@@ -65,9 +64,7 @@ __global__ __launch_bounds__(NT) void binary_overlap_kernel(const int64_t* a, co
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    unsigned long long v = c[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const unsigned long long v = wave_sum(c[i]);
     if (lane == 0) red[wv][i] = v;
   }
   __syncthreads();
@@ -182,11 +179,8 @@ __global__ __launch_bounds__(NT) void probs_mask_pass1(const float* probs, long 
     nl += pm == 1;
     nd += pm == 2;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    nl += __shfl_xor(nl, o, 64);
-    nd += __shfl_xor(nd, o, 64);
-  }
+  nl = wave_sum(nl);
+  nd = wave_sum(nd);
   if ((threadIdx.x & 63) == 0) {
     if (nl) atomicAdd(counts + 0, (unsigned long long)nl);
     if (nd) atomicAdd(counts + 1, (unsigned long long)nd);
@@ -236,10 +230,7 @@ int eunet_semantic_counts(const int64_t* pred, const int64_t* gt, int n, long lo
                           void* stream) {
   EUNET_REQUIRE(pred && gt && counts && n > 0 && hw > 0, "semantic_counts: bad args");
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(counts, 0, sizeof(int64_t) * 9 * n, s) != hipSuccess) {
-    eunet::set_error("semantic_counts: memset failed");
-    return EUNET_ERR_HIP;
-  }
+  if (!fill_async(counts, 0, sizeof(int64_t) * 9 * n, s, "semantic_counts")) return EUNET_ERR_HIP;
   long long bx = (hw + NT - 1) / NT;
   if (bx > 1024) bx = 1024;
   semantic_counts_kernel<<<dim3((unsigned)bx, n), NT, 0, s>>>(pred, gt, hw, (unsigned long long*)counts);
@@ -250,10 +241,7 @@ int eunet_semantic_counts(const int64_t* pred, const int64_t* gt, int n, long lo
 int eunet_binary_overlap(const int64_t* a, const int64_t* b, long long n, int64_t* out, void* stream) {
   EUNET_REQUIRE(a && b && out && n > 0, "binary_overlap: bad args");
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(out, 0, 4 * sizeof(int64_t), s) != hipSuccess) {
-    eunet::set_error("binary_overlap: memset failed");
-    return EUNET_ERR_HIP;
-  }
+  if (!fill_async(out, 0, 4 * sizeof(int64_t), s, "binary_overlap")) return EUNET_ERR_HIP;
   binary_overlap_kernel<<<grid_for(n) > 1024 ? 1024 : grid_for(n), NT, 0, s>>>(a, b, n, (unsigned long long*)out);
   EUNET_LAUNCH_CHECK("binary_overlap");
   return EUNET_OK;
@@ -294,10 +282,7 @@ int eunet_accumulate(float* acc, const float* p, long long n, int mode, float co
 int eunet_probs_to_mask(const float* probs, int k, int h, int w, int64_t* mask, int64_t* counts, void* stream) {
   EUNET_REQUIRE(probs && mask && counts && (k == 2 || k == 3) && h > 0 && w > 0, "probs_to_mask: bad args");
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s) != hipSuccess) {
-    eunet::set_error("probs_to_mask: memset failed");
-    return EUNET_ERR_HIP;
-  }
+  if (!fill_async(counts, 0, 2 * sizeof(int64_t), s, "probs_to_mask")) return EUNET_ERR_HIP;
   const long long hw = (long long)h * w;
   const unsigned g = grid_for(hw);
   unsigned long long* c = (unsigned long long*)counts;

@@ -14,12 +14,15 @@
 // outside[plane] and stored nowhere.  Every loop is bounded by the shapes, a label's rows or its vertex count; every
 // result is an integer and independent of the order in which the atomics land.
 #include "common.h"
+#include "labelmap.h"
 
 EUNET_DEBUG_UNIT(hull)
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == LM_NT, "labelmap.h sizes blocks of NT");
+constexpr int GRID_CAP = 4096;  // blocks of a grid-stride launch
 constexpr int PV = 4;             // pixels a lane holds
 constexpr int WAVE_PX = 64 * PV;  // pixels a wave holds
 constexpr int HC = EUNET_CELL_HULL_COLS;
@@ -333,12 +336,6 @@ __global__ __launch_bounds__(NT) void hull_chain_kernel(Layout t, const int* __r
   }
 }
 
-unsigned grid_for(long long threads, long long cap = 4096) {
-  long long b = (threads + NT - 1) / NT;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
 }  // namespace
 
 extern "C" {
@@ -348,7 +345,7 @@ int eunet_cell_hulls(const void* ids, int elem_bytes, int p, int h, int w, int n
                      void* stream) {
   EUNET_REQUIRE(ids && row_off && row_y0 && ext && verts && hull && outside, "cell_hulls: null pointer");
   EUNET_REQUIRE(elem_bytes == 4 || elem_bytes == 8, "cell_hulls: int32 or int64 ids (elem_bytes 4 or 8)");
-  EUNET_REQUIRE(p >= 1 && p <= 65535 && h >= 1 && h <= EUNET_EDT_MAX_SIDE && w >= 1 && w <= EUNET_EDT_MAX_SIDE,
+  EUNET_REQUIRE(plane_stack_ok(p, h, w, false),
                 "cell_hulls: bad shape (p 1..65535, h and w 1..%d)", EUNET_EDT_MAX_SIDE);
   EUNET_REQUIRE(n >= 0 && n <= EUNET_PAIRS_MAX_ID, "cell_hulls: n must lie in 0..%d (got %d)", EUNET_PAIRS_MAX_ID, n);
   EUNET_REQUIRE(((uintptr_t)row_off & 7u) == 0 && ((uintptr_t)row_y0 & 3u) == 0 && ((uintptr_t)ext & 7u) == 0 &&
@@ -359,13 +356,13 @@ int eunet_cell_hulls(const void* ids, int elem_bytes, int p, int h, int w, int n
   const Layout t = {(const long long*)row_off, row_y0, (long long)p * (n + 1), n};
   // R is on the device only; a label has at most h rows
   const long long most = t.L * (6ll * h + 4 + HC) + p;
-  hull_init_kernel<<<grid_for(most), NT, 0, s>>>(t, p, w, ext, verts, (long long*)hull, (long long*)outside);
-  const unsigned ge = grid_for((long long)p * h * ((w + WAVE_PX - 1) / WAVE_PX) * 64);
+  hull_init_kernel<<<grid_for(most, GRID_CAP), NT, 0, s>>>(t, p, w, ext, verts, (long long*)hull, (long long*)outside);
+  const unsigned ge = grid_for((long long)p * h * ((w + WAVE_PX - 1) / WAVE_PX) * 64, GRID_CAP);
   if (elem_bytes == 4)
     hull_extents_kernel<int32_t><<<ge, NT, 0, s>>>((const int32_t*)ids, p, h, w, t, ext, (long long*)outside);
   else
     hull_extents_kernel<int64_t><<<ge, NT, 0, s>>>((const int64_t*)ids, p, h, w, t, ext, (long long*)outside);
-  hull_chain_kernel<<<grid_for(t.L * 64), NT, 0, s>>>(t, ext, verts, (long long*)hull);
+  hull_chain_kernel<<<grid_for(t.L * 64, GRID_CAP), NT, 0, s>>>(t, ext, verts, (long long*)hull);
   EUNET_LAUNCH_CHECK("cell_hulls");
   return EUNET_OK;
 }

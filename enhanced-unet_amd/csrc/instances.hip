@@ -6,18 +6,15 @@
 // dilate, skimage.measure.label(connectivity=2), cv2.findContours + arcLength).
 // All of it is integer work: bit-exact, order-free (integer atomics), no floating point.
 #include "common.h"
+#include "labelmap.h"
 
 EUNET_DEBUG_UNIT(instances)
 
 namespace {
 
 constexpr int NT = 256;
-
-unsigned grid_for(long long n, long long cap = 8192) {
-  long long b = (n + NT - 1) / NT;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
+static_assert(NT == LM_NT, "labelmap.h sizes and scans blocks of NT");
+constexpr int GRID_CAP = 8192;  // blocks of a grid-stride launch
 
 // ---- bit-pack: masks [n][hw] uint8 (non-zero = set) -> packed [n][words] uint64, words = ceil(hw/64);
 // one wave64 ballot = one word; pixels past hw read as clear (zero-filled tail word); areas[n] += popcount
@@ -357,55 +354,12 @@ __global__ __launch_bounds__(NT) void cc_compress_kernel(long long total, int* p
 }
 
 // prefix sum over the root flags (parent[i] == i), in three launches: per-block counts of NT consecutive
-// pixels, one block scanning the counts, per-block ranks.  labels[root] = 1 + number of roots before it.
-__device__ __forceinline__ int block_exclusive_scan_flag(bool flag, int* total) {
-  __shared__ int wave_tot[NT / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int before = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_tot[wv] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < NT / 64; ++i) {
-    if (i < wv) off += wave_tot[i];
-    tot += wave_tot[i];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + before;
-}
-
+// pixels, one block scanning the counts (labelmap.h), per-block ranks.  labels[root] = 1 + number of roots before it.
 __global__ __launch_bounds__(NT) void cc_count_roots_kernel(const int* parent, long long total, int* block_count) {
   const long long i = (long long)blockIdx.x * NT + threadIdx.x;
   int tot;
   block_exclusive_scan_flag(i < total && parent[i] == (int)i, &tot);
   if (threadIdx.x == 0) block_count[blockIdx.x] = tot;
-}
-
-// one block: block_count[0..nb) -> exclusive offsets in place, total -> *n_out
-__global__ __launch_bounds__(NT) void cc_scan_blocks_kernel(int* block_count, int nb, int* n_out) {
-  __shared__ int buf[NT];
-  __shared__ int carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nb; base += NT) {
-    const int i = base + threadIdx.x;
-    const int v = i < nb ? block_count[i] : 0;
-    buf[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < NT; o <<= 1) {  // Hillis-Steele inclusive scan, log2(NT) static steps
-      const int t = threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
-      __syncthreads();
-      buf[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < nb) block_count[i] = carry + buf[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 0) carry += buf[NT - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *n_out = carry;
 }
 
 __global__ __launch_bounds__(NT) void cc_rank_roots_kernel(const int* parent, long long total, const int* block_off,
@@ -539,8 +493,7 @@ __global__ __launch_bounds__(NT) void mask_eq_kernel(const V* src, long long tot
     dst[i] = e ? 1 : 0;
     c += e;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, (unsigned long long)c);
 }
 
@@ -553,8 +506,7 @@ __global__ __launch_bounds__(NT) void mask_and_kernel(const uint8_t* a, const ui
     dst[i] = e ? 1 : 0;
     c += e;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, (unsigned long long)c);
 }
 
@@ -593,18 +545,10 @@ __global__ __launch_bounds__(NT) void expand_labels_kernel(const int* labels, lo
 template <typename V, bool BYVALUE, int CONN = 8>
 void launch_components(const V* v, int h, int w, int* parent, hipStream_t s) {
   const long long total = (long long)h * w;
-  const unsigned g = grid_for(total);
+  const unsigned g = grid_for(total, GRID_CAP);
   cc_init_kernel<V><<<g, NT, 0, s>>>(v, total, parent);
   cc_merge_kernel<V, BYVALUE, CONN><<<g, NT, 0, s>>>(v, h, w, parent);
   cc_compress_kernel<<<g, NT, 0, s>>>(total, parent);
-}
-
-bool zero_async(void* p, size_t bytes, hipStream_t s, const char* what) {
-  if (hipMemsetAsync(p, 0, bytes, s) != hipSuccess) {
-    eunet::set_error("%s: memset failed", what);
-    return false;
-  }
-  return true;
 }
 
 // the labelling behind eunet_label_components (CONN 8) and eunet_label_components_conn; the arguments are checked
@@ -612,15 +556,15 @@ template <int CONN>
 int label_components_impl(const uint8_t* img, int h, int w, int32_t* labels, int32_t* n_out, int32_t* areas,
                           int areas_cap, int32_t* ws, hipStream_t s, const char* what) {
   const long long total = (long long)h * w;
-  if (!zero_async(areas, sizeof(int32_t) * (size_t)areas_cap, s, what)) return EUNET_ERR_HIP;
+  if (!fill_async(areas, 0, sizeof(int32_t) * (size_t)areas_cap, s, what)) return EUNET_ERR_HIP;
   int* parent = ws;
   int* block_count = ws + total;
   const long long nb = (total + NT - 1) / NT;
   launch_components<uint8_t, false, CONN>(img, h, w, parent, s);
   cc_count_roots_kernel<<<(unsigned)nb, NT, 0, s>>>(parent, total, block_count);
-  cc_scan_blocks_kernel<<<1, NT, 0, s>>>(block_count, (int)nb, n_out);
+  scan_block_counts_kernel<NT><<<1, NT, 0, s>>>(block_count, (int)nb, n_out);
   cc_rank_roots_kernel<<<(unsigned)nb, NT, 0, s>>>(parent, total, block_count, labels);
-  cc_relabel_kernel<<<grid_for(total), NT, 0, s>>>(parent, total, labels, areas, areas_cap);
+  cc_relabel_kernel<<<grid_for(total, GRID_CAP), NT, 0, s>>>(parent, total, labels, areas, areas_cap);
   EUNET_LAUNCH_CHECK(what);
   return EUNET_OK;
 }
@@ -635,7 +579,7 @@ int eunet_pack_masks(const uint8_t* masks, int n, int h, int w, uint64_t* packed
   EUNET_REQUIRE(hw < (1ll << 31), "pack_masks: h * w must be below 2^31");
   EUNET_REQUIRE(n <= 65535, "pack_masks: at most 65535 masks per call");
   hipStream_t s = (hipStream_t)stream;
-  if (!zero_async(areas, sizeof(int64_t) * n, s, "pack_masks")) return EUNET_ERR_HIP;
+  if (!fill_async(areas, 0, sizeof(int64_t) * n, s, "pack_masks")) return EUNET_ERR_HIP;
   const long long words = (hw + 63) / 64;
   long long bx = (words + NT / 64 - 1) / (NT / 64);
   if (bx > 512) bx = 512;
@@ -652,7 +596,7 @@ int eunet_pack_masks_bbox(const uint8_t* masks, int n, int h, int w, uint64_t* p
   EUNET_REQUIRE(hw < (1ll << 31), "pack_masks_bbox: h * w must be below 2^31");
   EUNET_REQUIRE(n <= 65535, "pack_masks_bbox: at most 65535 masks per call");
   hipStream_t s = (hipStream_t)stream;
-  if (!zero_async(areas, sizeof(int64_t) * n, s, "pack_masks_bbox")) return EUNET_ERR_HIP;
+  if (!fill_async(areas, 0, sizeof(int64_t) * n, s, "pack_masks_bbox")) return EUNET_ERR_HIP;
   bbox_init_kernel<<<cdiv(n, NT), NT, 0, s>>>(bbox, n, h, w);
   const long long words = (hw + 63) / 64;
   long long bx = (words + NT / 64 - 1) / (NT / 64);
@@ -699,7 +643,7 @@ int eunet_pairwise_overlap(const uint64_t* a, int p, const uint64_t* b, int g, l
   const int tp = cdiv(p, PT), tg = cdiv(g, PT);
   EUNET_REQUIRE(tp <= 65535, "pairwise_overlap: too many masks");
   hipStream_t s = (hipStream_t)stream;
-  if (!zero_async(inter, sizeof(int64_t) * (size_t)p * g, s, "pairwise_overlap")) return EUNET_ERR_HIP;
+  if (!fill_async(inter, 0, sizeof(int64_t) * (size_t)p * g, s, "pairwise_overlap")) return EUNET_ERR_HIP;
   // split the word dimension when the pair tiles alone leave most of the 256 CUs idle (~4 blocks per CU)
   const long long chunks = (words + KC - 1) / KC;
   long long splits = 1024 / ((long long)tp * tg);
@@ -721,7 +665,7 @@ int eunet_morph_u8(const uint8_t* src, uint8_t* dst, uint8_t* tmp, int h, int w,
   EUNET_REQUIRE(src != dst, "morph_u8: not in place");
   EUNET_REQUIRE((long long)h * w < (1ll << 31), "morph_u8: h * w must be below 2^31");
   const MorphElem e = MORPH_ELEMS[elem];
-  const unsigned g = grid_for((long long)h * w);
+  const unsigned g = grid_for((long long)h * w, GRID_CAP);
   const uint8_t* in = src;
   for (int it = 0; it < iterations; ++it) {
     uint8_t* out = ((iterations - 1 - it) & 1) ? tmp : dst;  // the last pass writes dst
@@ -778,7 +722,7 @@ int eunet_outer_perimeter(const int32_t* labels, int h, int w, int n, int32_t* s
   hipStream_t s = (hipStream_t)stream;
   launch_components<int32_t, true>(labels, h, w, ws, s);
   label_stats_init_kernel<<<cdiv(n, NT), NT, 0, s>>>(stats, n, h, w);
-  label_stats_kernel<<<grid_for(total), NT, 0, s>>>(labels, ws, h, w, n, stats);
+  label_stats_kernel<<<grid_for(total, GRID_CAP), NT, 0, s>>>(labels, ws, h, w, n, stats);
   outer_border_kernel<<<cdiv(n, 64), 64, 0, s>>>(labels, h, w, n, stats);
   EUNET_LAUNCH_CHECK("outer_perimeter");
   return EUNET_OK;
@@ -789,7 +733,7 @@ int eunet_mask_eq(const void* src, int elem_bytes, long long n, long long value,
   EUNET_REQUIRE(src && dst && count && n > 0 && (elem_bytes == 4 || elem_bytes == 8),
                 "mask_eq: bad args (int32 or int64 source)");
   hipStream_t s = (hipStream_t)stream;
-  if (!zero_async(count, sizeof(int64_t), s, "mask_eq")) return EUNET_ERR_HIP;
+  if (!fill_async(count, 0, sizeof(int64_t), s, "mask_eq")) return EUNET_ERR_HIP;
   if (elem_bytes == 8)
     mask_eq_kernel<int64_t><<<grid_for(n, 1024), NT, 0, s>>>((const int64_t*)src, n, value, dst,
                                                              (unsigned long long*)count);
@@ -803,7 +747,7 @@ int eunet_mask_eq(const void* src, int elem_bytes, long long n, long long value,
 int eunet_mask_and(const uint8_t* a, const uint8_t* b, long long n, uint8_t* dst, int64_t* count, void* stream) {
   EUNET_REQUIRE(a && b && dst && count && n > 0, "mask_and: bad args");
   hipStream_t s = (hipStream_t)stream;
-  if (!zero_async(count, sizeof(int64_t), s, "mask_and")) return EUNET_ERR_HIP;
+  if (!fill_async(count, 0, sizeof(int64_t), s, "mask_and")) return EUNET_ERR_HIP;
   mask_and_kernel<<<grid_for(n, 1024), NT, 0, s>>>(a, b, n, dst, (unsigned long long*)count);
   EUNET_LAUNCH_CHECK("mask_and");
   return EUNET_OK;
@@ -811,7 +755,7 @@ int eunet_mask_and(const uint8_t* a, const uint8_t* b, long long n, uint8_t* dst
 
 int eunet_write_label(const uint8_t* mask, long long n, int label, int32_t* markers, void* stream) {
   EUNET_REQUIRE(mask && markers && n > 0 && label > 0, "write_label: bad args");
-  write_label_kernel<<<grid_for(n), NT, 0, (hipStream_t)stream>>>(mask, n, label, markers);
+  write_label_kernel<<<grid_for(n, GRID_CAP), NT, 0, (hipStream_t)stream>>>(mask, n, label, markers);
   EUNET_LAUNCH_CHECK("write_label");
   return EUNET_OK;
 }
@@ -819,7 +763,7 @@ int eunet_write_label(const uint8_t* mask, long long n, int label, int32_t* mark
 int eunet_relabel_table(const int32_t* labels, long long n, const int32_t* table, int n_labels, int32_t* markers,
                         void* stream) {
   EUNET_REQUIRE(labels && table && markers && n > 0 && n_labels > 0, "relabel_table: bad args");
-  relabel_table_kernel<<<grid_for(n), NT, 0, (hipStream_t)stream>>>(labels, n, table, n_labels, markers);
+  relabel_table_kernel<<<grid_for(n, GRID_CAP), NT, 0, (hipStream_t)stream>>>(labels, n, table, n_labels, markers);
   EUNET_LAUNCH_CHECK("relabel_table");
   return EUNET_OK;
 }
@@ -828,8 +772,8 @@ int eunet_expand_labels(const int32_t* labels, long long n, const int32_t* table
                         void* stream) {
   EUNET_REQUIRE(labels && table && out && n > 0 && n_labels > 0 && m > 0, "expand_labels: bad args");
   hipStream_t s = (hipStream_t)stream;
-  if (!zero_async(out, (size_t)m * (size_t)n, s, "expand_labels")) return EUNET_ERR_HIP;
-  expand_labels_kernel<<<grid_for(n), NT, 0, s>>>(labels, n, table, n_labels, m, out);
+  if (!fill_async(out, 0, (size_t)m * (size_t)n, s, "expand_labels")) return EUNET_ERR_HIP;
+  expand_labels_kernel<<<grid_for(n, GRID_CAP), NT, 0, s>>>(labels, n, table, n_labels, m, out);
   EUNET_LAUNCH_CHECK("expand_labels");
   return EUNET_OK;
 }

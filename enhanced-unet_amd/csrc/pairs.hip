@@ -10,44 +10,18 @@
 // Every loop is bounded by the shapes or by a constant, every result is an integer and independent of the order in
 // which the atomics land.
 #include "common.h"
+#include "labelmap.h"
 
 EUNET_DEBUG_UNIT(pairs)
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == LM_NT, "labelmap.h sizes blocks of NT");
+constexpr int GRID_CAP = 2048;           // blocks of a grid-stride launch
 constexpr int PV = 4;                    // pixels a lane holds
 constexpr int WAVE_PX = 64 * PV;         // pixels a wave holds
-constexpr int MAX_PROBE = 64;            // slots an insert looks at before it reports the table as full
-constexpr unsigned long long EMPTY = ~0ull;  // also the key of a pixel that is not counted: no pair has it
 constexpr long long ID_MAX = EUNET_PAIRS_MAX_ID;
-
-struct Table {
-  unsigned long long* keys;
-  int32_t* vals;
-  unsigned mask;   // capacity - 1, the capacity a power of two
-  int shift;       // 64 - log2(capacity)
-  int probes;      // min(capacity, MAX_PROBE)
-  int* overflow;
-};
-
-// vals[slot of key] += val.  Linear probing; a slot is claimed by the compare-and-swap that finds it empty, and a
-// key never leaves its slot, so two lanes with the same key meet in the same slot whatever their order.  An insert
-// that finds `probes` slots taken by other keys counts itself in *overflow and stores nothing: the host then reruns
-// the pass with a table twice as large.
-__device__ __forceinline__ void table_add(const Table& t, unsigned long long key, int val) {
-  unsigned slot = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> t.shift) & t.mask;
-  for (int probe = 0; probe < t.probes; ++probe) {
-    EUNET_DASSERT(slot <= t.mask);
-    const unsigned long long old = atomicCAS(t.keys + slot, EMPTY, key);
-    if (old == EMPTY || old == key) {
-      atomicAdd(t.vals + slot, val);
-      return;
-    }
-    slot = (slot + 1u) & t.mask;
-  }
-  atomicAdd(t.overflow, 1);
-}
 
 // PV consecutive ids starting at element i (i a multiple of PV).  VEC: the base pointer is 16-byte aligned, so a
 // lane whose PV pixels all lie inside reads them 16 bytes at a time; the last lane of the map reads what is there.
@@ -126,11 +100,10 @@ __global__ __launch_bounds__(NT) void pairs_kernel(const TA* __restrict__ a, con
       const unsigned rest = bm >> (j + 1);
       const int len = rest ? __ffs((int)rest) : PV - j + beyond;
       EUNET_DASSERT(len >= 1 && lane * PV + j + len <= WAVE_PX && i0 + j + len <= total);
-      table_add(t, key[j], len);
+      table_update<TableAdd>(t, key[j], len);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+  bad = wave_sum(bad);
   if (lane == 0 && bad) atomicAdd(invalid, (unsigned long long)bad);
 }
 
@@ -190,29 +163,14 @@ __global__ __launch_bounds__(NT) void labels_from_stack_kernel(const uint8_t* __
       out[i] = v[0];
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) over += __shfl_xor(over, o, 64);
+  over = wave_sum(over);
   if ((threadIdx.x & 63) == 0 && over) atomicAdd(overlap, (unsigned long long)over);
-}
-
-unsigned grid_for(long long n, long long cap = 2048) {
-  long long b = (n + NT - 1) / NT;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-bool fill_async(void* p, int byte, size_t bytes, hipStream_t s, const char* what) {
-  if (hipMemsetAsync(p, byte, bytes, s) != hipSuccess) {
-    eunet::set_error("%s: memset failed", what);
-    return false;
-  }
-  return true;
 }
 
 template <typename TA, typename TB>
 void launch_pairs(const void* a, const void* b, int p, long long hw, const Table& t, int64_t* invalid, hipStream_t s) {
   const long long chunks = ((long long)p * hw + WAVE_PX - 1) / WAVE_PX;
-  const unsigned g = grid_for(chunks * 64);
+  const unsigned g = grid_for(chunks * 64, GRID_CAP);
   const bool vec = (((uintptr_t)a | (uintptr_t)b) & 15u) == 0;
   if (vec)
     pairs_kernel<TA, TB, true><<<g, NT, 0, s>>>((const TA*)a, (const TB*)b, p, hw, t, (unsigned long long*)invalid);
@@ -229,24 +187,16 @@ int eunet_label_pairs(const void* a, int a_bytes, const void* b, int b_bytes, in
   EUNET_REQUIRE(a && b && keys && counts && overflow && invalid, "label_pairs: null pointer");
   EUNET_REQUIRE((a_bytes == 4 || a_bytes == 8) && (b_bytes == 4 || b_bytes == 8),
                 "label_pairs: int32 or int64 maps (a_bytes, b_bytes 4 or 8)");
-  EUNET_REQUIRE(p >= 1 && p <= 65535 && h >= 1 && h <= EUNET_EDT_MAX_SIDE && w >= 1 && w <= EUNET_EDT_MAX_SIDE &&
-                    (long long)p * h * w < (1ll << 31),
-                "label_pairs: bad shape (p 1..65535, h and w 1..%d, p h w < 2^31)", EUNET_EDT_MAX_SIDE);
-  EUNET_REQUIRE(capacity >= 2 && capacity <= (1ll << 30) && (capacity & (capacity - 1)) == 0,
-                "label_pairs: the capacity must be a power of two in 2..2^30 (got %lld)", capacity);
+  EUNET_REQUIRE(plane_stack_ok(p, h, w, true), "label_pairs: bad shape (p 1..65535, h and w 1..%d, p h w < 2^31)",
+                EUNET_EDT_MAX_SIDE);
   EUNET_REQUIRE(((uintptr_t)keys & 7u) == 0 && ((uintptr_t)invalid & 7u) == 0 &&
                     ((uintptr_t)a & (uintptr_t)(a_bytes - 1)) == 0 && ((uintptr_t)b & (uintptr_t)(b_bytes - 1)) == 0,
                 "label_pairs: misaligned pointer");
   const hipStream_t s = (hipStream_t)stream;
-  if (!fill_async(keys, 0xff, sizeof(int64_t) * (size_t)capacity, s, "label_pairs") ||
-      !fill_async(counts, 0, sizeof(int32_t) * (size_t)capacity, s, "label_pairs") ||
-      !fill_async(overflow, 0, sizeof(int32_t), s, "label_pairs") ||
-      !fill_async(invalid, 0, sizeof(int64_t), s, "label_pairs"))
-    return EUNET_ERR_HIP;
-  int log2cap = 0;
-  while ((1ll << log2cap) < capacity) ++log2cap;
-  const Table t = {(unsigned long long*)keys, counts, (unsigned)(capacity - 1), 64 - log2cap,
-                   (int)(capacity < MAX_PROBE ? capacity : MAX_PROBE), overflow};
+  Table t;
+  const int rc = table_init("label_pairs", keys, counts, capacity, overflow, s, &t);
+  if (rc != EUNET_OK) return rc;
+  if (!fill_async(invalid, 0, sizeof(int64_t), s, "label_pairs")) return EUNET_ERR_HIP;
   const long long hw = (long long)h * w;
   if (a_bytes == 4 && b_bytes == 4) launch_pairs<int32_t, int32_t>(a, b, p, hw, t, invalid, s);
   else if (a_bytes == 4) launch_pairs<int32_t, int64_t>(a, b, p, hw, t, invalid, s);
@@ -269,11 +219,11 @@ int eunet_labels_from_stack(const uint8_t* masks, int n, int h, int w, const int
   // 16 pixels per lane when every plane starts on a 16-byte boundary and no unit crosses the end
   const bool wide = hw % 16 == 0 && (((uintptr_t)masks | (uintptr_t)ignore | (uintptr_t)out) & 15u) == 0;
   if (wide)
-    labels_from_stack_kernel<16><<<grid_for(hw / 16), NT, 0, s>>>(masks, n, hw, ids, ignore, out,
-                                                                   (unsigned long long*)overlap);
+    labels_from_stack_kernel<16><<<grid_for(hw / 16, GRID_CAP), NT, 0, s>>>(masks, n, hw, ids, ignore, out,
+                                                                             (unsigned long long*)overlap);
   else
-    labels_from_stack_kernel<1><<<grid_for(hw), NT, 0, s>>>(masks, n, hw, ids, ignore, out,
-                                                             (unsigned long long*)overlap);
+    labels_from_stack_kernel<1><<<grid_for(hw, GRID_CAP), NT, 0, s>>>(masks, n, hw, ids, ignore, out,
+                                                                       (unsigned long long*)overlap);
   EUNET_LAUNCH_CHECK("labels_from_stack");
   return EUNET_OK;
 }

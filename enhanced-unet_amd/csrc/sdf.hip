@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "labelmap.h"
 
 EUNET_DEBUG_UNIT(sdf)
 
@@ -297,11 +298,6 @@ __global__ __launch_bounds__(NT) void bl_bwd_kernel(const float* logits, const f
   }
 }
 
-bool sdf_shape_ok(int n, int k, int h, int w) {
-  return n >= 1 && n <= 65535 && k >= 1 && k <= 3 && h >= 1 && h <= EUNET_EDT_MAX_SIDE && w >= 1 &&
-         w <= EUNET_EDT_MAX_SIDE;
-}
-
 // the shared argument rules of the two loss entries; fills cw and Kw
 bool loss_args(const char* what, const void* a, const void* b, const void* c, const void* d, int n, int k, int h,
                int w, int activation, const float* class_weight, Weights* cw, int* kw) {
@@ -337,8 +333,8 @@ extern "C" {
 
 int eunet_signed_distance_workspace_bytes(int n, int k, int h, int w, size_t* bytes) {
   EUNET_REQUIRE(bytes, "signed_distance_workspace_bytes: null pointer");
-  EUNET_REQUIRE(sdf_shape_ok(n, k, h, w), "signed_distance_workspace_bytes: bad shape (k 1..3, h and w 1..%d)",
-                EUNET_EDT_MAX_SIDE);
+  EUNET_REQUIRE(plane_stack_ok(n, h, w, false) && k >= 1 && k <= 3,
+                "signed_distance_workspace_bytes: bad shape (k 1..3, h and w 1..%d)", EUNET_EDT_MAX_SIDE);
   const size_t hw = (size_t)h * w;
   *bytes = (size_t)2 * n * k * hw * sizeof(int32_t) + (k == 1 ? (size_t)n * hw * sizeof(int64_t) : 0);
   return EUNET_OK;
@@ -347,8 +343,8 @@ int eunet_signed_distance_workspace_bytes(int n, int k, int h, int w, size_t* by
 int eunet_signed_distance(const int64_t* target, int n, int k, int h, int w, int ignore_index, float clip,
                           float scale, int32_t* ws, float* out, void* stream) {
   EUNET_REQUIRE(target && ws && out, "signed_distance: null pointer");
-  EUNET_REQUIRE(sdf_shape_ok(n, k, h, w), "signed_distance: bad shape (n 1..65535, k 1..3, h and w 1..%d)",
-                EUNET_EDT_MAX_SIDE);
+  EUNET_REQUIRE(plane_stack_ok(n, h, w, false) && k >= 1 && k <= 3,
+                "signed_distance: bad shape (n 1..65535, k 1..3, h and w 1..%d)", EUNET_EDT_MAX_SIDE);
   EUNET_REQUIRE(isfinite(clip) && clip >= 0.f, "signed_distance: clip must be finite and > 0 (0: no clamp)");
   EUNET_REQUIRE(isfinite(scale), "signed_distance: scale must be finite");
   EUNET_REQUIRE(k == 1 || ignore_index < 0 || ignore_index >= k,

@@ -8,7 +8,8 @@
 //   ws_jump_kernel     pointer jumping, in place, a fixed number of launches that stop working once a round
 //                      changed nothing (a device flag per round, no host read)
 //   ws_first_kernel    the raster-first pixel of every basin (atomicMin, one per run of a basin in a wave)
-//   ws_count / ws_scan / ws_rank / ws_fill   basins numbered 1..nb per plane in raster order of their first pixel
+//   ws_count / scan_block_counts (labelmap.h) / ws_rank / ws_fill   basins numbered 1..nb per plane in raster order
+//                      of their first pixel
 //   ws_peaks_kernel    root and peak of every basin, for the host's merge
 //   ws_saddles_kernel  max over the 8-adjacent pixel pairs of two basins of min(D, D), into an open-addressing hash
 //                      table keyed by the pair (atomicCAS insert, atomicMax value); equal pairs of a wave go in once
@@ -17,24 +18,19 @@
 // Every loop is bounded by the shapes or by a constant, no block waits on another, every result is an integer and
 // independent of the order in which the atomics land.
 #include "common.h"
+#include "labelmap.h"
 
 EUNET_DEBUG_UNIT(watershed)
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == LM_NT, "labelmap.h sizes and scans blocks of NT");
+constexpr int GRID_CAP = 2048;      // blocks along x of a grid-stride launch
 constexpr int UP_NT = 64;           // a wave per block
 constexpr int UP_W = UP_NT - 2;     // columns a wave writes: its first and last lane hold the neighbouring columns
 constexpr int UP_ROWS = 32;         // rows a wave walks down
-constexpr int MAX_PROBE = 64;       // slots an insert looks at before it reports the table as full
 constexpr int MIN_MATES = 4;        // lanes that must share a pair before the wave combines them
-constexpr unsigned long long EMPTY = ~0ull;
-
-unsigned grid_for(long long n, long long cap = 2048) {
-  long long b = (n + NT - 1) / NT;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
 
 // grid (ceil(w / UP_W), ceil(h / UP_ROWS), p).  key(q) = (D[q], -q): a candidate replaces the best so far only when
 // its D is strictly larger, and the candidates are visited in ascending linear index, so the smallest index among
@@ -131,25 +127,7 @@ __global__ __launch_bounds__(NT) void ws_first_kernel(const int32_t* root_all, l
 }
 
 // prefix sum over the first-pixel flags, as instances.hip numbers components: per-block counts of NT consecutive
-// pixels, one block per plane scanning its counts, per-block ranks.
-__device__ __forceinline__ int block_exclusive_scan_flag(bool flag, int* total) {
-  __shared__ int wave_tot[NT / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int before = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_tot[wv] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < NT / 64; ++i) {
-    if (i < wv) off += wave_tot[i];
-    tot += wave_tot[i];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + before;
-}
-
+// pixels, one block per plane scanning its counts, per-block ranks (labelmap.h).
 __device__ __forceinline__ bool is_first(const int32_t* root, const int32_t* first, long long hw, long long i) {
   if (i >= hw) return false;
   const int r = root[i];
@@ -166,32 +144,6 @@ __global__ __launch_bounds__(NT) void ws_count_kernel(const int32_t* root_all, c
   block_exclusive_scan_flag(is_first(root_all + base, first_all + base, hw, (long long)blockIdx.x * NT + threadIdx.x),
                             &tot);
   if (threadIdx.x == 0) block_count[(long long)blockIdx.y * gridDim.x + blockIdx.x] = tot;
-}
-
-// grid (p): block_count[plane][0..nbp) -> exclusive offsets in place, total -> counts[plane]
-__global__ __launch_bounds__(NT) void ws_scan_kernel(int* block_count_all, int nbp, int32_t* counts) {
-  __shared__ int buf[NT];
-  __shared__ int carry;
-  int* block_count = block_count_all + (long long)blockIdx.x * nbp;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nbp; base += NT) {
-    const int i = base + threadIdx.x;
-    const int v = i < nbp ? block_count[i] : 0;
-    buf[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < NT; o <<= 1) {  // Hillis-Steele inclusive scan, log2(NT) static steps
-      const int t = threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
-      __syncthreads();
-      buf[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < nbp) block_count[i] = carry + buf[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 0) carry += buf[NT - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[blockIdx.x] = carry;
 }
 
 // grid (nbp, p): basin[first pixel] = 1 + the number of first pixels before it in its plane
@@ -242,33 +194,6 @@ __global__ __launch_bounds__(NT) void ws_peaks_kernel(const int32_t* dist_all, c
   }
 }
 
-struct Table {
-  unsigned long long* keys;
-  int32_t* vals;
-  unsigned mask;   // capacity - 1, the capacity a power of two
-  int shift;       // 64 - log2(capacity)
-  int probes;      // min(capacity, MAX_PROBE)
-  int* overflow;
-};
-
-// vals[slot of key] = max(itself, val).  Linear probing; a slot is claimed by the compare-and-swap that finds it
-// empty, and a key never leaves its slot, so two lanes with the same key meet in the same slot whatever their
-// order.  An insert that finds `probes` slots taken by other keys counts itself in *overflow and stores nothing:
-// the host then reruns the pass with a table twice as large.
-__device__ __forceinline__ void table_put(const Table& t, unsigned long long key, int val) {
-  unsigned slot = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> t.shift) & t.mask;
-  for (int probe = 0; probe < t.probes; ++probe) {
-    EUNET_DASSERT(slot <= t.mask);
-    const unsigned long long old = atomicCAS(t.keys + slot, EMPTY, key);
-    if (old == EMPTY || old == key) {
-      atomicMax(t.vals + slot, val);
-      return;
-    }
-    slot = (slot + 1u) & t.mask;
-  }
-  atomicAdd(t.overflow, 1);
-}
-
 // Every lane brings at most one (pair, value).  A run of a basin border puts the same pair on many lanes of a wave:
 // the lanes that share the first pending lane's pair are reduced with a wave maximum and inserted once, at most
 // twice in a row; what is left inserts for itself.  A maximum: exact either way.  Whole waves only.
@@ -282,17 +207,12 @@ __device__ __forceinline__ void wave_put(const Table& t, bool has, unsigned long
     const bool mate = has && key == lk;
     const unsigned long long mates = __ballot(mate);
     if (__popcll(mates) < MIN_MATES) break;
-    int m = mate ? val : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int other = __shfl_xor(m, o, 64);
-      m = other > m ? other : m;
-    }
-    if (lane == lead) table_put(t, lk, m);
+    const int m = wave_max(mate ? val : 0);
+    if (lane == lead) table_update<TableMax>(t, lk, m);
     has = has && !mate;
     todo &= ~mates;
   }
-  if (has) table_put(t, key, val);
+  if (has) table_update<TableMax>(t, key, val);
 }
 
 // grid (gx, p), whole waves.  Each foreground pixel looks at its E, SW, S and SE neighbours: every unordered pair of
@@ -368,23 +288,10 @@ __global__ __launch_bounds__(NT) void ws_relabel_kernel(const int32_t* basin_all
   }
 }
 
-bool shape_ok(int p, int h, int w) {
-  return p >= 1 && p <= 65535 && h >= 1 && h <= EUNET_EDT_MAX_SIDE && w >= 1 && w <= EUNET_EDT_MAX_SIDE &&
-         (long long)p * h * w < (1ll << 31);
-}
-
 int jump_rounds(long long hw) {
   int r = 0;
   while ((1ll << r) < hw) ++r;
   return r + 1;  // ceil(log2(hw)) rounds finish every chain; one more so that a 1-pixel plane has a round too
-}
-
-bool fill_async(void* p, int byte, size_t bytes, hipStream_t s, const char* what) {
-  if (hipMemsetAsync(p, byte, bytes, s) != hipSuccess) {
-    eunet::set_error("%s: memset failed", what);
-    return false;
-  }
-  return true;
 }
 
 }  // namespace
@@ -393,8 +300,8 @@ extern "C" {
 
 int eunet_watershed_workspace_bytes(int p, int h, int w, size_t* bytes) {
   EUNET_REQUIRE(bytes, "watershed_workspace_bytes: null pointer");
-  EUNET_REQUIRE(shape_ok(p, h, w), "watershed_workspace_bytes: bad shape (p 1..65535, h and w 1..%d, p h w < 2^31)",
-                EUNET_EDT_MAX_SIDE);
+  EUNET_REQUIRE(plane_stack_ok(p, h, w, true),
+                "watershed_workspace_bytes: bad shape (p 1..65535, h and w 1..%d, p h w < 2^31)", EUNET_EDT_MAX_SIDE);
   const long long hw = (long long)h * w;
   const long long nbp = (hw + NT - 1) / NT;
   *bytes = sizeof(int32_t) * (size_t)(2 * (long long)p * hw + (long long)p * nbp + EUNET_WATERSHED_FLAG_WORDS);
@@ -404,7 +311,7 @@ int eunet_watershed_workspace_bytes(int p, int h, int w, size_t* bytes) {
 int eunet_watershed_basins(const int32_t* dist, int p, int h, int w, int32_t* basin, int32_t* counts, int32_t* ws,
                            void* stream) {
   EUNET_REQUIRE(dist && basin && counts && ws, "watershed_basins: null pointer");
-  EUNET_REQUIRE(shape_ok(p, h, w), "watershed_basins: bad shape (p 1..65535, h and w 1..%d, p h w < 2^31)",
+  EUNET_REQUIRE(plane_stack_ok(p, h, w, true), "watershed_basins: bad shape (p 1..65535, h and w 1..%d, p h w < 2^31)",
                 EUNET_EDT_MAX_SIDE);
   EUNET_REQUIRE(dist != basin, "watershed_basins: not in place");
   const hipStream_t s = (hipStream_t)stream;
@@ -421,13 +328,13 @@ int eunet_watershed_basins(const int32_t* dist, int p, int h, int w, int32_t* ba
     return EUNET_ERR_HIP;
   ws_up_kernel<<<dim3((unsigned)cdiv(w, UP_W), (unsigned)cdiv(h, UP_ROWS), (unsigned)p), UP_NT, 0, s>>>(dist, h, w,
                                                                                                        root);
-  const dim3 gp(grid_for(hw), (unsigned)p);
+  const dim3 gp(grid_for(hw, GRID_CAP), (unsigned)p);
   for (int r = 0; r < rounds; ++r)
     ws_jump_kernel<<<gp, NT, 0, s>>>(root, hw, r ? flags + r - 1 : nullptr, flags + r);
   ws_first_kernel<<<gp, NT, 0, s>>>(root, hw, first);
   const dim3 gb((unsigned)nbp, (unsigned)p);
   ws_count_kernel<<<gb, NT, 0, s>>>(root, first, hw, block_count);
-  ws_scan_kernel<<<(unsigned)p, NT, 0, s>>>(block_count, (int)nbp, counts);
+  scan_block_counts_kernel<NT><<<(unsigned)p, NT, 0, s>>>(block_count, (int)nbp, counts);
   ws_rank_kernel<<<gb, NT, 0, s>>>(root, first, hw, block_count, basin);
   ws_fill_kernel<<<gp, NT, 0, s>>>(root, first, hw, basin);
   EUNET_LAUNCH_CHECK("watershed_basins");
@@ -437,10 +344,10 @@ int eunet_watershed_basins(const int32_t* dist, int p, int h, int w, int32_t* ba
 int eunet_watershed_peaks(const int32_t* dist, const int32_t* basin, const int32_t* ws, int p, int h, int w,
                           const int32_t* offs, int nb_total, int32_t* root, int32_t* peak, void* stream) {
   EUNET_REQUIRE(dist && basin && ws && offs && root && peak, "watershed_peaks: null pointer");
-  EUNET_REQUIRE(shape_ok(p, h, w) && nb_total >= 1, "watershed_peaks: bad shape");
+  EUNET_REQUIRE(plane_stack_ok(p, h, w, true) && nb_total >= 1, "watershed_peaks: bad shape");
   const long long hw = (long long)h * w;
-  ws_peaks_kernel<<<dim3(grid_for(hw), (unsigned)p), NT, 0, (hipStream_t)stream>>>(dist, ws, basin, hw, offs, nb_total,
-                                                                                  root, peak);
+  ws_peaks_kernel<<<dim3(grid_for(hw, GRID_CAP), (unsigned)p), NT, 0, (hipStream_t)stream>>>(
+      dist, ws, basin, hw, offs, nb_total, root, peak);
   EUNET_LAUNCH_CHECK("watershed_peaks");
   return EUNET_OK;
 }
@@ -448,20 +355,13 @@ int eunet_watershed_peaks(const int32_t* dist, const int32_t* basin, const int32
 int eunet_watershed_saddles(const int32_t* dist, const int32_t* basin, int p, int h, int w, const int32_t* offs,
                             int64_t* keys, int32_t* vals, long long capacity, int32_t* overflow, void* stream) {
   EUNET_REQUIRE(dist && basin && offs && keys && vals && overflow, "watershed_saddles: null pointer");
-  EUNET_REQUIRE(shape_ok(p, h, w), "watershed_saddles: bad shape");
-  EUNET_REQUIRE(capacity >= 2 && capacity <= (1ll << 30) && (capacity & (capacity - 1)) == 0,
-                "watershed_saddles: the capacity must be a power of two in 2..2^30 (got %lld)", capacity);
+  EUNET_REQUIRE(plane_stack_ok(p, h, w, true), "watershed_saddles: bad shape");
   EUNET_REQUIRE(((uintptr_t)keys & 7u) == 0, "watershed_saddles: misaligned keys");
   const hipStream_t s = (hipStream_t)stream;
-  if (!fill_async(keys, 0xff, sizeof(int64_t) * (size_t)capacity, s, "watershed_saddles") ||
-      !fill_async(vals, 0, sizeof(int32_t) * (size_t)capacity, s, "watershed_saddles") ||
-      !fill_async(overflow, 0, sizeof(int32_t), s, "watershed_saddles"))
-    return EUNET_ERR_HIP;
-  int log2cap = 0;
-  while ((1ll << log2cap) < capacity) ++log2cap;
-  const Table t = {(unsigned long long*)keys, vals, (unsigned)(capacity - 1), 64 - log2cap,
-                   (int)(capacity < MAX_PROBE ? capacity : MAX_PROBE), overflow};
-  ws_saddles_kernel<<<dim3(grid_for((long long)h * w), (unsigned)p), NT, 0, s>>>(dist, basin, h, w, offs, t);
+  Table t;
+  const int rc = table_init("watershed_saddles", keys, vals, capacity, overflow, s, &t);
+  if (rc != EUNET_OK) return rc;
+  ws_saddles_kernel<<<dim3(grid_for((long long)h * w, GRID_CAP), (unsigned)p), NT, 0, s>>>(dist, basin, h, w, offs, t);
   EUNET_LAUNCH_CHECK("watershed_saddles");
   return EUNET_OK;
 }
@@ -469,11 +369,12 @@ int eunet_watershed_saddles(const int32_t* dist, const int32_t* basin, int p, in
 int eunet_watershed_relabel(const int32_t* basin, int p, int h, int w, const int32_t* offs, const int32_t* table,
                             int nb_total, int32_t* ids, int32_t* areas, int amax, void* stream) {
   EUNET_REQUIRE(basin && offs && table && ids && areas, "watershed_relabel: null pointer");
-  EUNET_REQUIRE(shape_ok(p, h, w) && nb_total >= 1 && amax >= 1, "watershed_relabel: bad shape");
+  EUNET_REQUIRE(plane_stack_ok(p, h, w, true) && nb_total >= 1 && amax >= 1, "watershed_relabel: bad shape");
   const hipStream_t s = (hipStream_t)stream;
   if (!fill_async(areas, 0, sizeof(int32_t) * (size_t)p * (size_t)amax, s, "watershed_relabel")) return EUNET_ERR_HIP;
   const long long hw = (long long)h * w;
-  ws_relabel_kernel<<<dim3(grid_for(hw), (unsigned)p), NT, 0, s>>>(basin, hw, offs, table, nb_total, ids, areas, amax);
+  ws_relabel_kernel<<<dim3(grid_for(hw, GRID_CAP), (unsigned)p), NT, 0, s>>>(basin, hw, offs, table, nb_total, ids, areas,
+                                                                             amax);
   EUNET_LAUNCH_CHECK("watershed_relabel");
   return EUNET_OK;
 }

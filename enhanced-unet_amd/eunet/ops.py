@@ -1001,6 +1001,39 @@ def distance_transform_sq(labels, values, mode, out):
 _distance_transform_sq_op = distance_transform_sq  # torch.ops.eunet.distance_transform_sq writes into out
 
 
+def _plane_shape(name, what, shape, bound_pixels, planes="p", verb="are"):
+    """An [h, w] or [p, h, w] shape as (p, h, w), within the plane-stack rule of the label-map kernels (csrc/labelmap.h,
+    plane_stack_ok): p 1..65535, h and w 1..EDT_MAX_SIDE, and with bound_pixels p h w < 2^31."""
+    p, h, w = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+    side = _lib.EDT_MAX_SIDE
+    if not (1 <= p <= 65535 and 1 <= h <= side and 1 <= w <= side and (not bound_pixels or p * h * w < 2 ** 31)):
+        raise ValueError(f"{name}: {what} {tuple(shape)} {verb} outside {planes} 1..65535, h and w 1..{side}"
+                         + (", p h w < 2^31" if bound_pixels else ""))
+    return p, h, w
+
+
+def _table_cap(name, capacity):
+    """The _table_capacity argument of an op with a growing hash table: None, or a power of two in 2..2^30."""
+    if capacity is None:
+        return None
+    cap = int(capacity)
+    if cap < 2 or cap > 2 ** 30 or cap & (cap - 1):
+        raise ValueError(f"{name}: _table_capacity must be a power of two in 2..2^30, got {capacity!r}")
+    return cap
+
+
+def _fill_table(name, what, cap, launch):
+    """Runs launch(cap) -> (inserts that found no slot, what the caller reads back) with a table of cap slots, twice as
+    large each time, until every insert found one -> (cap, what the last launch read back)."""
+    while True:
+        overflow, back = launch(cap)
+        if overflow == 0:
+            return cap, back
+        if cap >= 2 ** 30:
+            raise _lib.EunetError(f"{name}: the {what} table overflows at 2^30 slots")
+        cap *= 2  # nothing was dropped silently: the pass is run again with room for every pair
+
+
 def _int64_maps(name, what, t, device=None):
     """t as a contiguous int64 [n, h, w] device map within the transform's limits (and whether it came as [h, w])."""
     if not isinstance(t, torch.Tensor):
@@ -1016,9 +1049,7 @@ def _int64_maps(name, what, t, device=None):
     single = t.dim() == 2
     if single:
         t = t.unsqueeze(0)
-    n, h, w = t.shape
-    if not (1 <= n <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE):
-        raise ValueError(f"{name}: {what} {tuple(t.shape)} is outside n 1..65535, h and w 1..{_lib.EDT_MAX_SIDE}")
+    _plane_shape(name, what, t.shape, False, planes="n", verb="is")
     return t, single
 
 
@@ -1512,29 +1543,12 @@ def watershed_from_distance(dist_sq, depth: float = 1.0, out=None, _table_capaci
     of two; it is doubled until every pair fits), for tests."""
     import numpy as np
     name = "watershed_from_distance"
-    if not isinstance(dist_sq, torch.Tensor):
-        raise ValueError(f"{name}: dist_sq must be a tensor")
-    if not dist_sq.is_cuda:
-        raise ValueError(f"{name}: dist_sq must live on a GPU, got {dist_sq.device}")
-    if dist_sq.dtype != torch.int32:
-        raise ValueError(f"{name}: dist_sq must be int32, got {dist_sq.dtype}")
-    if dist_sq.dim() not in (2, 3):
-        raise ValueError(f"{name}: dist_sq must be [h, w] or [p, h, w], got {tuple(dist_sq.shape)}")
-    if not dist_sq.is_contiguous():
-        raise ValueError(f"{name}: dist_sq must be contiguous")
+    _id_maps(name, "dist_sq", dist_sq, (torch.int32,))
     single = dist_sq.dim() == 2
     d = dist_sq.unsqueeze(0) if single else dist_sq
-    p, h, w = d.shape
-    if not (1 <= p <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE and p * h * w < 2 ** 31):
-        raise ValueError(f"{name}: dist_sq {tuple(dist_sq.shape)} is outside p 1..65535, h and w "
-                         f"1..{_lib.EDT_MAX_SIDE}, p h w < 2^31")
+    p, h, w = _plane_shape(name, "dist_sq", dist_sq.shape, True, verb="is")
     depth = _watershed_depth(name, depth)
-    if _table_capacity is None:
-        cap = None
-    else:
-        cap = int(_table_capacity)
-        if cap < 2 or cap > 2 ** 30 or cap & (cap - 1):
-            raise ValueError(f"{name}: _table_capacity must be a power of two in 2..2^30, got {_table_capacity!r}")
+    cap = _table_cap(name, _table_capacity)
     dev = d.device
     if out is None:
         ids = torch.empty(tuple(dist_sq.shape), dtype=torch.int32, device=dev)
@@ -1566,18 +1580,17 @@ def watershed_from_distance(dist_sq, depth: float = 1.0, out=None, _table_capaci
         cap = 64
         while cap < 8 * nb_total:
             cap *= 2
-    while True:
+
+    def saddles(cap):
         keys = torch.empty(cap, dtype=torch.int64, device=dev)
         vals = torch.empty(cap + 1, dtype=torch.int32, device=dev)  # [cap]: the overflow count
         with kprof.timed("watershed_saddles", 0.0, p * hw * 4.0 * 10):
             call("eunet_watershed_saddles", _ptr(d), _ptr(ids), p, h, w, _ptr(offs_d), _ptr(keys), _ptr(vals), cap,
                  _ptr(vals[cap:]), _stream())
         v = vals.cpu().numpy()
-        if v[cap] == 0:
-            break
-        if cap >= 2 ** 30:
-            raise _lib.EunetError(f"{name}: the saddle table overflows at 2^30 slots")
-        cap *= 2  # nothing was dropped silently: the pass is run again with room for every pair
+        return v[cap], (keys, v)
+
+    cap, (keys, v) = _fill_table(name, "saddle", cap, saddles)
     k = keys.cpu().numpy()
     used = k != -1
     rp = rootpeak.cpu().numpy()
@@ -1620,13 +1633,14 @@ PAIRS_FIRST_CAPACITY = 4096
 PAIRS_MAX_ID = _lib.PAIRS_MAX_ID  # the largest id of a map
 
 
-def _id_maps(name, what, t):
+def _id_maps(name, what, t, dtypes=(torch.int32, torch.int64)):
+    """t as a contiguous [h, w] or [p, h, w] device map of one of the dtypes."""
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{name}: {what} must be a tensor")
     if not t.is_cuda:
         raise ValueError(f"{name}: {what} must live on a GPU, got {t.device}")
-    if t.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{name}: {what} must be int32 or int64, got {t.dtype}")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{name}: {what} must be {' or '.join(str(d)[6:] for d in dtypes)}, got {t.dtype}")
     if t.dim() not in (2, 3):
         raise ValueError(f"{name}: {what} must be [h, w] or [p, h, w], got {tuple(t.shape)}")
     if not t.is_contiguous():
@@ -1649,19 +1663,12 @@ def label_pairs(a, b, _table_capacity=None):
         raise ValueError(f"{name}: the maps differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")
     if a.device != b.device:
         raise ValueError(f"{name}: the maps live on different devices: {a.device} vs {b.device}")
-    p, h, w = (1,) + tuple(a.shape) if a.dim() == 2 else tuple(a.shape)
-    if not (1 <= p <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE and p * h * w < 2 ** 31):
-        raise ValueError(f"{name}: maps {tuple(a.shape)} are outside p 1..65535, h and w 1..{_lib.EDT_MAX_SIDE}, "
-                         "p h w < 2^31")
-    if _table_capacity is None:
-        cap = PAIRS_FIRST_CAPACITY
-    else:
-        cap = int(_table_capacity)
-        if cap < 2 or cap > 2 ** 30 or cap & (cap - 1):
-            raise ValueError(f"{name}: _table_capacity must be a power of two in 2..2^30, got {_table_capacity!r}")
+    p, h, w = _plane_shape(name, "maps", a.shape, True)
+    cap = _table_cap(name, _table_capacity) or PAIRS_FIRST_CAPACITY
     dev = a.device
     nbytes = float(p * h * w * (a.element_size() + b.element_size()))
-    while True:
+
+    def pairs(cap):
         # one int64 buffer: the keys, then [cap] the invalid count, then the int32 counts and [cap] the overflow
         buf = torch.empty(cap + 1 + (cap + 2) // 2, dtype=torch.int64, device=dev)
         vals = buf[cap + 1:].view(torch.int32)
@@ -1673,11 +1680,9 @@ def label_pairs(a, b, _table_capacity=None):
         v = host[cap + 1:].view(np.int32)
         if invalid:
             raise ValueError(f"{name}: {invalid} pixel(s) hold an id above 2^24 - 1")
-        if v[cap] == 0:
-            break
-        if cap >= 2 ** 30:
-            raise _lib.EunetError(f"{name}: the pair table overflows at 2^30 slots")
-        cap *= 2  # nothing was dropped silently: the pass is run again with room for every pair
+        return v[cap], (k, v)
+
+    cap, (k, v) = _fill_table(name, "pair", cap, pairs)
     used = k != -1
     k, n = k[used].view(np.uint64), v[:cap][used].astype(np.int64)  # unsigned: a plane above 32767 sets the top bit
     order = np.argsort(k, kind="stable")  # plane, a, b are the key's fields from the top: key order is row order
@@ -1739,9 +1744,7 @@ def cell_stats(ids, n: int, image=None):
     import operator
     name = "cell_stats"
     ids = _id_maps(name, "ids", ids)
-    p, h, w = (1,) + tuple(ids.shape) if ids.dim() == 2 else tuple(ids.shape)
-    if not (1 <= p <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE):
-        raise ValueError(f"{name}: ids {tuple(ids.shape)} are outside p 1..65535, h and w 1..{_lib.EDT_MAX_SIDE}")
+    p, h, w = _plane_shape(name, "ids", ids.shape, False)
     try:
         n = operator.index(n)
     except TypeError:
@@ -1793,9 +1796,7 @@ def cell_hulls(ids, stats):
     import numpy as np
     name = "cell_hulls"
     ids = _id_maps(name, "ids", ids)
-    p, h, w = (1,) + tuple(ids.shape) if ids.dim() == 2 else tuple(ids.shape)
-    if not (1 <= p <= 65535 and 1 <= h <= _lib.EDT_MAX_SIDE and 1 <= w <= _lib.EDT_MAX_SIDE):
-        raise ValueError(f"{name}: ids {tuple(ids.shape)} are outside p 1..65535, h and w 1..{_lib.EDT_MAX_SIDE}")
+    p, h, w = _plane_shape(name, "ids", ids.shape, False)
     if not isinstance(stats, dict) or "geom" not in stats or "shape" not in stats:
         raise ValueError(f"{name}: stats must be cell_stats' dict (\"geom\", \"shape\")")
     if tuple(int(v) for v in stats["shape"]) != (h, w):

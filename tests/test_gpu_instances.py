@@ -131,6 +131,19 @@ def test_label_components_matches_scipy_numbering(name):
         assert n_ref == 1
 
 
+@pytest.mark.parametrize("connectivity", [8, 4])
+def test_label_components_scans_more_blocks_than_one_pass_holds(connectivity):
+    """257 x 256 pixels are 257 blocks of 256: the scan of the per-block root counts takes its second pass of 256
+    counts and carries the first pass's total into it.  Noise of the `noise` case's density, against scipy."""
+    from eunet import ops
+    img = (np.random.default_rng(11).random((257, 256)) < 0.45).astype(np.uint8)
+    ref, n_ref = ndimage.label(img, structure=ONES3 if connectivity == 8 else None)
+    labels, n, areas = ops.label_components(dev(img), connectivity=connectivity)
+    assert n == n_ref and np.setdiff1d(ref[256], ref[:256]).size > 0   # the 257th block numbers roots too
+    assert np.array_equal(labels.cpu().numpy(), ref.astype(np.int32))
+    assert np.array_equal(areas.cpu().numpy(), np.bincount(ref.ravel(), minlength=n_ref + 1)[1:])
+
+
 # ---- morphology ---------------------------------------------------------------------------------------
 def _morph_ref(img, k, dilate, iterations):
     out = img

@@ -93,6 +93,32 @@ def test_infinite_depth_is_label_components(shape):
         assert counts.tolist() == [n] and torch.equal(ids, labels.cpu()) and torch.equal(areas, lab_areas.cpu()), kind
 
 
+def test_two_planes_of_more_blocks_than_one_scan_pass_holds():
+    """257 x 256 pixels are 257 blocks of 256 per plane: the scan of the per-block counts takes its second pass, and
+    the second plane's counts start 257 entries in.  Too large for the restatement's loops: depth inf against
+    label_components, depth 0 as a refinement of it."""
+    from eunet import ops
+    shape = (257, 256)
+    masks = [_mask(shape, kind) for kind in ("random0.5", "discs")]
+    stack = torch.from_numpy(np.stack(masks).astype(np.int64)).to(DEV)
+    D = ops.distance_transform_sq(stack, [1], "ne")[:, 0].cpu().numpy()
+    assert D.shape == (2,) + shape
+    whole, whole_counts, whole_areas = _run(D, math.inf)
+    fine, fine_counts, fine_areas = _run(D, 0.0)
+    for i, m in enumerate(masks):
+        labels, n, lab_areas = ops.label_components(torch.from_numpy(m.astype(np.uint8)).to(DEV))
+        assert int(whole_counts[i]) == n and torch.equal(whole[i], labels.cpu()), i
+        assert torch.equal(whole_areas[i, :n], lab_areas.cpu()) and int(whole_areas[i, n:].abs().sum()) == 0, i
+        f, c = fine[i].numpy(), whole[i].numpy()
+        assert np.array_equal(f > 0, m), i
+        nf = int(fine_counts[i])
+        assert nf >= n and np.array_equal(np.unique(f[f > 0]), np.arange(1, nf + 1)), i
+        parent = np.zeros(nf + 1, np.int64)
+        parent[f[f > 0]] = c[f > 0]
+        assert np.array_equal(parent[f], c), i   # every fine region lies in one component
+        assert np.array_equal(fine_areas[i, :nf].numpy(), np.bincount(f.ravel(), minlength=nf + 1)[1:]), i
+
+
 @pytest.mark.parametrize("depth", DEPTHS)
 def test_a_batch_of_three_planes(depth):
     """Planes with many, few and no basins side by side: each keeps its own numbering, the areas are padded with 0."""
