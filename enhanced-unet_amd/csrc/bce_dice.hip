@@ -26,39 +26,16 @@
 // multiplication by 1.0f is exact and the rest of the expression is the unweighted one, so m = 1 gives the
 // unweighted bits.  WEIGHTED = false is the code as it was.
 #include "common.h"
+#include "pixelloss.h"
+#include "labelmap.h"
 
 EUNET_DEBUG_UNIT(bcedice)
 
 namespace {
-constexpr int NT = 256;
-constexpr int LPIX = 1024;  // pixels per partial tile: 4 per thread
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
 
 const eunet_bce_dice_params kDefaultParams = {
     {1.f, 1.f, 1.f}, {1.f, 1.f, 1.f}, {1.f, 1.f, 1.f}, 1.f, 1.f, 1e-6f, EUNET_NO_IGNORE, EUNET_BCE_TARGET_AUTO};
-
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
-
-// sig(x), sig(-x), sp(x), sp(-x) from one exp: no overflow and no cancellation at +-100
-struct Sig {
-  float p, q, spp, spn;
-};
-template <bool WITH_SP>
-__device__ __forceinline__ Sig sigmoid_terms(float x) {
-  const float e = expf(-fabsf(x));
-  const float r = 1.f / (1.f + e);
-  const float hi = r, lo = e * r;
-  Sig s;
-  s.p = x >= 0.f ? hi : lo;
-  s.q = x >= 0.f ? lo : hi;
-  if (WITH_SP) {
-    const float l = log1pf(e);
-    s.spp = fmaxf(x, 0.f) + l;
-    s.spn = fmaxf(-x, 0.f) + l;
-  } else {
-    s.spp = s.spn = 0.f;
-  }
-  return s;
-}
 
 // 0 ignored, 1 valid, 2 out of range
 __device__ __forceinline__ int classify(int64_t traw, int K, const eunet_bce_dice_params& prm) {
@@ -92,20 +69,23 @@ __device__ __forceinline__ void fwd_px(const float (&x)[K], int64_t traw, float 
   }
 }
 
+// The visit and the loads are written out here, not taken from pixelloss.h (pl_tile_visit, pl_load4, pl_px): through
+// them the compiler packs and contracts the accumulations differently and K = 3 takes one more register, across a
+// waves-per-SIMD step (profiles/pixelloss_resources.txt).  The tail is the shared one.
 template <int K, bool VEC, bool WEIGHTED>
-__global__ __launch_bounds__(NT) void bce_dice_fwd_kernel(const float* logits, const int64_t* target, const float* pw,
-                                                          int HW, eunet_bce_dice_params prm, float* part) {
-  constexpr int NV = 3 + 3 * K;
-  __shared__ float red[4][NV];
-  const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+__global__ __launch_bounds__(PL_NT) void bce_dice_fwd_kernel(const float* logits, const int64_t* target,
+                                                             const float* pw, int HW, eunet_bce_dice_params prm,
+                                                             float* part) {
+  constexpr int NV = pl_nv(K);
+  const int n = blockIdx.y, tid = threadIdx.x;
   const float* lg = logits + (long long)n * K * HW;
   const int64_t* tg = target + (long long)n * HW;
   const float* wg = WEIGHTED ? pw + (long long)n * HW : nullptr;
   float acc[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) acc[i] = 0.f;
-  const int p0 = blockIdx.x * LPIX;
-  const int p1 = min(HW, p0 + LPIX);
+  const int p0 = blockIdx.x * PL_LPIX;
+  const int p1 = min(HW, p0 + PL_LPIX);
   if (VEC) {  // HW % 4 == 0: every plane and every 4-pixel group starts on 16 bytes
     const int p = p0 + tid * 4;
     if (p < p1) {
@@ -127,7 +107,7 @@ __global__ __launch_bounds__(NT) void bce_dice_fwd_kernel(const float* logits, c
       }
     }
   } else {
-    for (int p = p0 + tid; p < p1; p += NT) {
+    for (int p = p0 + tid; p < p1; p += PL_NT) {
       EUNET_DASSERT(p < HW);
       float x[K];
 #pragma unroll
@@ -135,50 +115,25 @@ __global__ __launch_bounds__(NT) void bce_dice_fwd_kernel(const float* logits, c
       fwd_px<K, WEIGHTED>(x, tg[p], WEIGHTED ? wg[p] : 1.f, prm, acc);
     }
   }
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float s = wave_sum(acc[i]);
-    if (lane == 0) red[wv][i] = s;
-  }
-  __syncthreads();
-  if (tid < NV)
-    part[((long long)n * gridDim.x + blockIdx.x) * NV + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  pl_block_row<NV>(acc, part);
 }
 
-// One 256-thread block: per sample, the threads stride over the tile partials (fp64), a fixed-order
-// LDS tree combines them (deterministic), thread 0 forms the sample's terms; the batch sums are
+// One 256-thread block: thread 0 forms each sample's terms from its sums (pl_sample_sum); the batch sums are
 // taken in sample order.
 template <int K>
 __global__ __launch_bounds__(256) void bce_dice_finalize_kernel(const float* part, int tiles, int N,
                                                                 eunet_bce_dice_params prm, float* sums,
                                                                 float* loss, float* parts) {
-  constexpr int NV = 3 + 3 * K;
-  __shared__ double red[256][NV];
+  constexpr int NV = pl_nv(K);
   __shared__ double dice_s[64], bnum[64], vcnt[64], nbad[64];
   const int tid = threadIdx.x;
   EUNET_DASSERT(N <= 64);
   for (int n = 0; n < N; ++n) {
     double v[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = 0.0;
-    for (int t = tid; t < tiles; t += 256)
-#pragma unroll
-      for (int i = 0; i < NV; ++i) v[i] += (double)part[((long long)n * tiles + t) * NV + i];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) red[tid][i] = v[i];
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if (tid < off)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) red[tid][i] += red[tid + off][i];
-      __syncthreads();
-    }
+    pl_sample_sum<NV>(part, tiles, n, v);
     if (tid == 0) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        v[i] = red[0][i];
-        sums[n * NV + i] = (float)v[i];
-      }
+      for (int i = 0; i < NV; ++i) sums[n * NV + i] = (float)v[i];
       const double sm = (double)prm.smooth;
       double dice = 0.0;
       for (int c = 0; c < K; ++c) {
@@ -249,59 +204,48 @@ __device__ __forceinline__ void bwd_px(const float (&x)[K], int64_t traw, const 
 // VEC: one thread per group of 4 pixels (HW % 4 == 0, so a group never straddles two samples)
 // WEIGHTED: bwd_px gets cb * m(x) for cb
 template <int K, bool VEC, bool WEIGHTED>
-__global__ __launch_bounds__(NT) void bce_dice_bwd_kernel(const float* logits, const int64_t* target, const float* pw,
-                                                          int N, int HW, eunet_bce_dice_params prm, const float* sums,
-                                                          const float* gloss, float* glog) {
-  constexpr int NV = 3 + 3 * K;
-  constexpr int PER = VEC ? 4 : 1;
-  const long long id = ((long long)blockIdx.x * NT + threadIdx.x) * PER;
-  const long long total = (long long)N * HW;
-  if (id >= total) return;
-  EUNET_DASSERT(id + PER <= total);
-  const int n = (int)(id / HW);
-  const int p = (int)(id - (long long)n * HW);
-  EUNET_DASSERT(n < N && p + PER <= HW);
-  const float* lg = logits + (long long)n * K * HW + p;
-  float* gl = glog + (long long)n * K * HW + p;
+__global__ __launch_bounds__(PL_NT) void bce_dice_bwd_kernel(const float* logits, const int64_t* target,
+                                                             const float* pw, int N, int HW,
+                                                             eunet_bce_dice_params prm, const float* sums,
+                                                             const float* gloss, float* glog) {
+  constexpr int NV = pl_nv(K), PER = VEC ? 4 : 1;
+  long long id;
+  int n, p;
+  if (!pl_bwd_split<PER>(N, HW, id, n, p)) return;
   const DiceCoef<K> dc = dice_coef<K>(sums + n * NV, N, prm);
   const float vt = sums[N * NV];
   const float cb = prm.w_bce / ((float)K * fmaxf(vt, 1.f));
   const float g0 = gloss[0];
+  const float* lg = logits + (long long)n * K * HW + p;
+  float* gl = glog + (long long)n * K * HW + p;
   if (VEC) {
-    f32x4 xv[K], gv[K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) xv[c] = *reinterpret_cast<const f32x4*>(lg + (long long)c * HW);
-    const i64x2 t01 = *reinterpret_cast<const i64x2*>(target + id);
-    const i64x2 t23 = *reinterpret_cast<const i64x2*>(target + id + 2);
-    const int64_t tr[4] = {t01[0], t01[1], t23[0], t23[1]};
-    f32x4 wv = {1.f, 1.f, 1.f, 1.f};
-    if (WEIGHTED) wv = *reinterpret_cast<const f32x4*>(pw + id);
+    f32x4 xv[K], gv[K], wv[1] = {{1.f, 1.f, 1.f, 1.f}};
+    int64_t tr[4];
+    pl_load4<K>(lg, HW, xv);
+    pl_load4(target + id, tr);
+    if (WEIGHTED) pl_load4<1>(pw + id, HW, wv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float x[K], g[K];
-#pragma unroll
-      for (int c = 0; c < K; ++c) x[c] = xv[c][j];
-      bwd_px<K>(x, tr[j], prm, dc, WEIGHTED ? cb * wv[j] : cb, g0, g);
+      pl_px<K>(xv, j, x);
+      bwd_px<K>(x, tr[j], prm, dc, WEIGHTED ? cb * wv[0][j] : cb, g0, g);
 #pragma unroll
       for (int c = 0; c < K; ++c) gv[c][j] = g[c];
     }
-#pragma unroll
-    for (int c = 0; c < K; ++c) *reinterpret_cast<f32x4*>(gl + (long long)c * HW) = gv[c];
+    pl_store4<K>(gl, HW, gv);
   } else {
     float x[K], g[K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) x[c] = lg[(long long)c * HW];
+    pl_load<K>(lg, HW, x);
     bwd_px<K>(x, target[id], prm, dc, WEIGHTED ? cb * pw[id] : cb, g0, g);
-#pragma unroll
-    for (int c = 0; c < K; ++c) gl[(long long)c * HW] = g[c];
+    pl_store<K>(gl, HW, g);
   }
 }
 
 template <int K>
-__global__ __launch_bounds__(NT) void sigmoid_crop_kernel(const float* logits, int hp, int wp, int h, int w,
+__global__ __launch_bounds__(PL_NT) void sigmoid_crop_kernel(const float* logits, int hp, int wp, int h, int w,
                                                           int flip_h, int flip_w, float* probs) {
   const long long total = (long long)h * w;
-  for (long long id = (long long)blockIdx.x * NT + threadIdx.x; id < total; id += (long long)gridDim.x * NT) {
+  for (long long id = (long long)blockIdx.x * PL_NT + threadIdx.x; id < total; id += (long long)gridDim.x * PL_NT) {
     const int x = (int)(id % w), yy = (int)(id / w);
     const int sy = flip_h ? h - 1 - yy : yy, sx = flip_w ? w - 1 - x : x;
     EUNET_DASSERT(sy >= 0 && sy < hp && sx >= 0 && sx < wp);
@@ -312,9 +256,9 @@ __global__ __launch_bounds__(NT) void sigmoid_crop_kernel(const float* logits, i
 }
 
 template <int K>
-__global__ __launch_bounds__(NT) void probs_threshold_kernel(const float* probs, long long hw, float thr,
-                                                             int64_t* mask) {
-  for (long long id = (long long)blockIdx.x * NT + threadIdx.x; id < hw; id += (long long)gridDim.x * NT) {
+__global__ __launch_bounds__(PL_NT) void probs_threshold_kernel(const float* probs, long long hw, float thr,
+                                                                int64_t* mask) {
+  for (long long id = (long long)blockIdx.x * PL_NT + threadIdx.x; id < hw; id += (long long)gridDim.x * PL_NT) {
     int64_t m;
     if (K == 1) {
       m = probs[id] >= thr ? 1 : 0;
@@ -332,11 +276,6 @@ __global__ __launch_bounds__(NT) void probs_threshold_kernel(const float* probs,
     }
     mask[id] = m;
   }
-}
-
-inline unsigned grid_for(long long n) {
-  const long long b = (n + NT - 1) / NT;
-  return (unsigned)(b < 2048 ? (b > 0 ? b : 1) : 2048);
 }
 
 // the params of a call with target_mode resolved for K; false (error set) when they are refused
@@ -360,54 +299,43 @@ bool resolve(const eunet_bce_dice_params* params, int k, eunet_bce_dice_params* 
 int bce_dice_fwd_launch(const float* logits, const int64_t* target, const float* pw, int n, int k, int h, int w,
                         const eunet_bce_dice_params* params, float* sums, float* loss, float* parts, void* ws,
                         void* stream, const char* what) {
-  EUNET_REQUIRE(logits && target && sums && loss && ws && n > 0 && n <= 64 && k >= 1 && k <= 3 && h > 0 && w > 0 &&
-                    (long long)h * w < (1ll << 31) - LPIX,
-                "%s: bad args (N <= 64, K <= 3)", what);
+  EUNET_REQUIRE(logits && target && sums && loss && ws && pl_shape_ok(n, k, h, w), "%s: bad args (" PL_SHAPE_RULE ")",
+                what);
   eunet_bce_dice_params prm;
   if (!resolve(params, k, &prm, what)) return EUNET_ERR_INVALID;
-  const int HW = h * w, tiles = cdiv(HW, LPIX);
+  const int HW = h * w, tiles = pl_tiles(HW);
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(tiles, n);
-  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)target % 16 == 0) &&
-                   ((uintptr_t)pw % 16 == 0);
-#define BK(KK, VV)                                                                                        \
-  if (pw)                                                                                                 \
-    bce_dice_fwd_kernel<KK, VV, true><<<grid, NT, 0, s>>>(logits, target, pw, HW, prm, (float*)ws);       \
-  else                                                                                                    \
-    bce_dice_fwd_kernel<KK, VV, false><<<grid, NT, 0, s>>>(logits, target, nullptr, HW, prm, (float*)ws);
-#define BF(KK)                                                                                            \
-  if (vec) { BK(KK, true) } else { BK(KK, false) }                                                        \
-  bce_dice_finalize_kernel<KK><<<1, 256, 0, s>>>((const float*)ws, tiles, n, prm, sums, loss, parts);
-  if (k == 1) { BF(1) } else if (k == 2) { BF(2) } else { BF(3) }
-#undef BF
-#undef BK
+  by_k(k, [&](auto kc) {
+    constexpr int K = decltype(kc)::value;
+    by_flag(pl_vec_ok(HW, {logits, target, pw}), [&](auto vc) {
+      by_flag(pw != nullptr, [&](auto wc) {
+        bce_dice_fwd_kernel<K, decltype(vc)::value, decltype(wc)::value>
+            <<<dim3(tiles, n), PL_NT, 0, s>>>(logits, target, pw, HW, prm, (float*)ws);
+      });
+    });
+    bce_dice_finalize_kernel<K><<<1, 256, 0, s>>>((const float*)ws, tiles, n, prm, sums, loss, parts);
+  });
   return eunet::check_launch(what);
 }
 
 int bce_dice_bwd_launch(const float* logits, const int64_t* target, const float* pw, int n, int k, int h, int w,
                         const eunet_bce_dice_params* params, const float* sums, const float* gloss, float* glogits,
                         void* stream, const char* what) {
-  EUNET_REQUIRE(logits && target && sums && gloss && glogits && n > 0 && n <= 64 && k >= 1 && k <= 3 && h > 0 &&
-                    w > 0 && (long long)h * w < (1ll << 31) - LPIX,
-                "%s: bad args (N <= 64, K <= 3)", what);
+  EUNET_REQUIRE(logits && target && sums && gloss && glogits && pl_shape_ok(n, k, h, w),
+                "%s: bad args (" PL_SHAPE_RULE ")", what);
   eunet_bce_dice_params prm;
   if (!resolve(params, k, &prm, what)) return EUNET_ERR_INVALID;
   const int HW = h * w;
-  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)target % 16 == 0) &&
-                   ((uintptr_t)glogits % 16 == 0) && ((uintptr_t)pw % 16 == 0);
-  const long long threads = (long long)n * HW / (vec ? 4 : 1);
-  const unsigned g = (unsigned)((threads + NT - 1) / NT);
+  const bool vec = pl_vec_ok(HW, {logits, target, glogits, pw});
   hipStream_t s = (hipStream_t)stream;
-#define BK(KK, VV)                                                                                               \
-  if (pw)                                                                                                        \
-    bce_dice_bwd_kernel<KK, VV, true><<<g, NT, 0, s>>>(logits, target, pw, n, HW, prm, sums, gloss, glogits);    \
-  else                                                                                                           \
-    bce_dice_bwd_kernel<KK, VV, false><<<g, NT, 0, s>>>(logits, target, nullptr, n, HW, prm, sums, gloss, glogits);
-#define BB(KK) \
-  if (vec) { BK(KK, true) } else { BK(KK, false) }
-  if (k == 1) { BB(1) } else if (k == 2) { BB(2) } else { BB(3) }
-#undef BB
-#undef BK
+  by_k(k, [&](auto kc) {
+    by_flag(vec, [&](auto vc) {
+      by_flag(pw != nullptr, [&](auto wc) {
+        bce_dice_bwd_kernel<decltype(kc)::value, decltype(vc)::value, decltype(wc)::value>
+            <<<pl_bwd_grid(n, HW, vec), PL_NT, 0, s>>>(logits, target, pw, n, HW, prm, sums, gloss, glogits);
+      });
+    });
+  });
   return eunet::check_launch(what);
 }
 
@@ -423,14 +351,13 @@ int eunet_bce_dice_default_params(eunet_bce_dice_params* prm) {
 
 int eunet_bce_dice_sums_len(int n, int k, int* len) {
   EUNET_REQUIRE(len && n > 0 && k >= 1 && k <= 3, "bce_dice_sums_len: bad args");
-  *len = n * (3 + 3 * k) + 2;
+  *len = pl_sums_len(n, pl_nv(k));
   return EUNET_OK;
 }
 
 int eunet_bce_dice_workspace_bytes(int n, int k, int h, int w, size_t* bytes) {
   EUNET_REQUIRE(bytes && n > 0 && k >= 1 && k <= 3 && h > 0 && w > 0, "bce_dice_workspace_bytes: bad args");
-  const int tiles = cdiv(h * w, LPIX);
-  *bytes = (size_t)n * tiles * (3 + 3 * k) * sizeof(float);
+  *bytes = pl_workspace_bytes(n, h, w, pl_nv(k));
   return EUNET_OK;
 }
 
@@ -468,25 +395,22 @@ int eunet_sigmoid_crop(const float* logits, int k, int hp, int wp, int h, int w,
                        float* probs, void* stream) {
   EUNET_REQUIRE(logits && probs && k >= 1 && k <= 3 && h > 0 && w > 0 && h <= hp && w <= wp,
                 "sigmoid_crop: bad args (K must be 1..3, crop inside the map)");
-  const unsigned g = grid_for((long long)h * w);
   hipStream_t s = (hipStream_t)stream;
-  if (k == 1) sigmoid_crop_kernel<1><<<g, NT, 0, s>>>(logits, hp, wp, h, w, flip_h, flip_w, probs);
-  else if (k == 2) sigmoid_crop_kernel<2><<<g, NT, 0, s>>>(logits, hp, wp, h, w, flip_h, flip_w, probs);
-  else sigmoid_crop_kernel<3><<<g, NT, 0, s>>>(logits, hp, wp, h, w, flip_h, flip_w, probs);
-  EUNET_LAUNCH_CHECK("sigmoid_crop");
-  return EUNET_OK;
+  by_k(k, [&](auto kc) {
+    sigmoid_crop_kernel<decltype(kc)::value>
+        <<<grid_for((long long)h * w, 2048), PL_NT, 0, s>>>(logits, hp, wp, h, w, flip_h, flip_w, probs);
+  });
+  return eunet::check_launch("sigmoid_crop");
 }
 
 int eunet_probs_threshold(const float* probs, int k, int h, int w, float threshold, int64_t* mask, void* stream) {
   EUNET_REQUIRE(probs && mask && k >= 1 && k <= 3 && h > 0 && w > 0, "probs_threshold: bad args (K must be 1..3)");
   const long long hw = (long long)h * w;
-  const unsigned g = grid_for(hw);
   hipStream_t s = (hipStream_t)stream;
-  if (k == 1) probs_threshold_kernel<1><<<g, NT, 0, s>>>(probs, hw, threshold, mask);
-  else if (k == 2) probs_threshold_kernel<2><<<g, NT, 0, s>>>(probs, hw, threshold, mask);
-  else probs_threshold_kernel<3><<<g, NT, 0, s>>>(probs, hw, threshold, mask);
-  EUNET_LAUNCH_CHECK("probs_threshold");
-  return EUNET_OK;
+  by_k(k, [&](auto kc) {
+    probs_threshold_kernel<decltype(kc)::value><<<grid_for(hw, 2048), PL_NT, 0, s>>>(probs, hw, threshold, mask);
+  });
+  return eunet::check_launch("probs_threshold");
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 #include <stdint.h>
@@ -295,6 +296,19 @@ template <class F>
 inline void by_dtype(int dtype, F&& f) {
   if (dtype == EUNET_BF16) f(bf16_t{});
   else f(float{});
+}
+// f(std::integral_constant<int, K>{}) with K = k (validated before: 1..3), the class count of a kernel template
+template <class F>
+inline void by_k(int k, F&& f) {
+  if (k == 1) f(std::integral_constant<int, 1>{});
+  else if (k == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 3>{});
+}
+// f(std::true_type{}) or f(std::false_type{}): a bool template argument chosen at the launch
+template <class F>
+inline void by_flag(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 // the typed base pointer of a view; null for an absent (optional) view
 template <class T>

@@ -26,36 +26,16 @@
 // focal coefficient (backward): a multiplication by 1.0f is exact and the rest of the expression is
 // the unweighted one, so m = 1 gives the unweighted bits.  WEIGHTED = false is the code as it was.
 #include "common.h"
+#include "pixelloss.h"
+
+EUNET_DEBUG_UNIT(loss)
 
 namespace {
-constexpr int NT = 256;
-constexpr int LPIX = 1024;  // pixels per partial tile
-
 // the Trainer's enhanced_unet configuration (train_eval.py:74-87, 140, 164, 175)
 const eunet_loss_params kReferenceParams = {
     {1.f, 20.f, 10.f}, {1.f, 8.f, 5.f}, 5.f, EUNET_NO_IGNORE, {1.f, 15.f, 8.f}, {1.f, 12.f, 6.f}, 0.7f, 2.5f, 2.5f, 1.f, 3.f, 0};
 
 constexpr float EPS = 1e-6f;
-
-template <int K>
-__device__ __forceinline__ void softmax_px(const float* lg, long long plane, float (&p)[K], float& lse_m, float& m) {
-  float l[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) l[k] = lg[k * plane];
-  m = l[0];
-#pragma unroll
-  for (int k = 1; k < K; ++k) m = fmaxf(m, l[k]);
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    p[k] = expf(l[k] - m);
-    s += p[k];
-  }
-  const float inv = 1.f / s;
-#pragma unroll
-  for (int k = 0; k < K; ++k) p[k] *= inv;
-  lse_m = logf(s);  // log sum exp(l - m)
-}
 
 // (1-pt)^gamma and (1-pt)^(gamma-1); gamma 5 (the reference's) in the product form the
 // fixtures were pinned with, small integers by repeated products, otherwise powf
@@ -79,22 +59,25 @@ __device__ __forceinline__ void focal_pow(float om, float gamma, float& pg, floa
 }
 
 template <int K, bool WEIGHTED>
-__global__ __launch_bounds__(NT) void loss_fwd_kernel(const float* logits, const int64_t* target, const float* pw,
-                                                      int HW, eunet_loss_params prm, float* part) {
-  constexpr int NV = 3 + 3 * K;  // focal sum, I/S/T per class, ce-weight sum, bad-target count
-  __shared__ float red[4][NV];
-  const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+__global__ __launch_bounds__(PL_NT) void loss_fwd_kernel(const float* logits, const int64_t* target, const float* pw,
+                                                         int HW, eunet_loss_params prm, float* part) {
+  constexpr int NV = pl_nv(K);  // focal sum, I/S/T per class, ce-weight sum, bad-target count
+  const int n = blockIdx.y;
   const long long plane = HW;
   const float* lg = logits + (long long)n * K * HW;
   const int64_t* tg = target + (long long)n * HW;
   float acc[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) acc[i] = 0.f;
-  const int p0 = blockIdx.x * LPIX;
-  const int p1 = min(HW, p0 + LPIX);
-  for (int p = p0 + tid; p < p1; p += NT) {
-    float pr[K], lse_m, m;
-    softmax_px<K>(lg + p, plane, pr, lse_m, m);
+  // the scalar visit of pl_tile_visit<false>, written out: through the callable the K = 3 kernel contracts three
+  // more accumulations and its sums lose bit identity with the pinned ones (tools/bitcmp.py --losses)
+  const int p0 = blockIdx.x * PL_LPIX;
+  const int p1 = min(HW, p0 + PL_LPIX);
+  for (int p = p0 + threadIdx.x; p < p1; p += PL_NT) {
+    EUNET_DASSERT(p < HW);
+    float x[K], pr[K], lse_m, m;
+    pl_load<K>(lg, HW, x, p);
+    softmax_px<K>(x, pr, m, lse_m);
     const int64_t traw = tg[p];
     const bool ign = traw == (int64_t)prm.ignore_index;
     const bool valid = !ign && traw >= 0 && traw < K;
@@ -119,49 +102,25 @@ __global__ __launch_bounds__(NT) void loss_fwd_kernel(const float* logits, const
       acc[1 + 2 * K + k] += tk;
     }
   }
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float s = wave_sum(acc[i]);
-    if (lane == 0) red[wv][i] = s;
-  }
-  __syncthreads();
-  if (tid < NV)
-    part[((long long)n * gridDim.x + blockIdx.x) * NV + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  pl_block_row<NV>(acc, part);
 }
 
-// One 256-thread block: per sample, the threads stride over the tile partials (fp64),
-// a fixed-order LDS tree combines them (deterministic), thread 0 forms the sample's
-// terms; the batch sums are taken in sample order.
+// One 256-thread block: thread 0 forms each sample's terms from its sums (pl_sample_sum); the batch sums are
+// taken in sample order.
 template <int K>
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* part, int tiles, int N, int HW,
                                                             eunet_loss_params prm, float* sums, float* loss,
                                                             float* parts) {
-  constexpr int NV = 3 + 3 * K;
-  __shared__ double red[256][NV];
+  constexpr int NV = pl_nv(K);
   __shared__ double per[64], fnum[64], fden[64], nbad[64];
   const int tid = threadIdx.x;
+  EUNET_DASSERT(N <= 64);
   for (int n = 0; n < N; ++n) {
     double v[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = 0.0;
-    for (int t = tid; t < tiles; t += 256)
-#pragma unroll
-      for (int i = 0; i < NV; ++i) v[i] += (double)part[((long long)n * tiles + t) * NV + i];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) red[tid][i] = v[i];
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if (tid < off)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) red[tid][i] += red[tid + off][i];
-      __syncthreads();
-    }
+    pl_sample_sum<NV>(part, tiles, n, v);
     if (tid == 0) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        v[i] = red[0][i];
-        sums[n * NV + i] = (float)v[i];
-      }
+      for (int i = 0; i < NV; ++i) sums[n * NV + i] = (float)v[i];
       double dice = 0.0, tv = 0.0;
       for (int k = 0; k < K; ++k) {
         const double I = v[1 + k], S = v[1 + K + k], T = v[1 + 2 * K + k];
@@ -203,15 +162,15 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* part, i
 template <int K, bool WEIGHTED>
 __global__ void loss_bwd_kernel(const float* logits, const int64_t* target, const float* pw, int N, int HW,
                                 eunet_loss_params prm, const float* sums, const float* gloss, float* glog) {
-  constexpr int NV = 3 + 3 * K;
-  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= (long long)N * HW) return;
-  const int n = (int)(id / HW);
-  const int p = (int)(id - (long long)n * HW);
+  constexpr int NV = pl_nv(K);
+  long long id;
+  int n, p;
+  if (!pl_bwd_split<1>(N, HW, id, n, p)) return;
   const long long plane = HW;
   const float* lg = logits + (long long)n * K * HW + p;
-  float pr[K], lse_m, m;
-  softmax_px<K>(lg, plane, pr, lse_m, m);
+  float x[K], pr[K], lse_m, m;
+  pl_load<K>(lg, HW, x);
+  softmax_px<K>(x, pr, m, lse_m);
   const int64_t traw = target[id];
   const bool valid = traw != (int64_t)prm.ignore_index && traw >= 0 && traw < K;
   const int t = valid ? (int)traw : 0;
@@ -243,6 +202,8 @@ __global__ void loss_bwd_kernel(const float* logits, const int64_t* target, cons
     sdp += pr[k] * dp[k];
   }
   const float g0 = gloss[0];
+  // stored from the loop, not staged for pl_store: staged, the K = 3 kernel contracts the other product of g
+  // into its multiply-add and a last bit changes (tools/bitcmp.py --losses)
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const float tk = (valid && t == k) ? 1.f : 0.f;
@@ -263,14 +224,13 @@ int eunet_loss_reference_params(eunet_loss_params* prm) {
 
 int eunet_loss_sums_len(int n, int k, int* len) {
   EUNET_REQUIRE(len && n > 0 && k >= 1 && k <= 3, "loss_sums_len: bad args");
-  *len = n * (3 + 3 * k) + 2;
+  *len = pl_sums_len(n, pl_nv(k));
   return EUNET_OK;
 }
 
 int eunet_loss_workspace_bytes(int n, int k, int h, int w, size_t* bytes) {
   EUNET_REQUIRE(bytes && n > 0 && k >= 1 && k <= 3 && h > 0 && w > 0, "loss_workspace_bytes: bad args");
-  const int tiles = cdiv(h * w, LPIX);
-  *bytes = (size_t)n * tiles * (3 + 3 * k) * sizeof(float);
+  *bytes = pl_workspace_bytes(n, h, w, pl_nv(k));
   return EUNET_OK;
 }
 
@@ -281,39 +241,38 @@ namespace {
 int loss_fwd_launch(const float* logits, const int64_t* target, const float* pw, int n, int k, int h, int w,
                     const eunet_loss_params* params, float* sums, float* loss, float* parts, void* ws, void* stream,
                     const char* what) {
+  EUNET_REQUIRE(logits && target && sums && loss && ws && pl_shape_ok(n, k, h, w), "%s: bad args (" PL_SHAPE_RULE ")",
+                what);
   const eunet_loss_params prm = params ? *params : kReferenceParams;
   EUNET_REQUIRE(prm.class_div > 0.f, "%s: class_div must be > 0", what);
   EUNET_REQUIRE(!pw || prm.focal_norm == 0,
                 "%s: focal_norm = 1 with a pixel weight is not defined (its denominator would need a definition)", what);
-  const int HW = h * w, tiles = cdiv(HW, LPIX);
+  const int HW = h * w, tiles = pl_tiles(HW);
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(tiles, n);
-#define LF(KK)                                                                                        \
-  if (pw)                                                                                             \
-    loss_fwd_kernel<KK, true><<<grid, NT, 0, s>>>(logits, target, pw, HW, prm, (float*)ws);           \
-  else                                                                                                \
-    loss_fwd_kernel<KK, false><<<grid, NT, 0, s>>>(logits, target, nullptr, HW, prm, (float*)ws);     \
-  loss_finalize_kernel<KK><<<1, 256, 0, s>>>((const float*)ws, tiles, n, HW, prm, sums, loss, parts);
-  if (k == 1) { LF(1) } else if (k == 2) { LF(2) } else { LF(3) }
-#undef LF
+  by_k(k, [&](auto kc) {
+    constexpr int K = decltype(kc)::value;
+    by_flag(pw != nullptr, [&](auto wc) {
+      loss_fwd_kernel<K, decltype(wc)::value><<<dim3(tiles, n), PL_NT, 0, s>>>(logits, target, pw, HW, prm, (float*)ws);
+    });
+    loss_finalize_kernel<K><<<1, 256, 0, s>>>((const float*)ws, tiles, n, HW, prm, sums, loss, parts);
+  });
   return eunet::check_launch(what);
 }
 
 int loss_bwd_launch(const float* logits, const int64_t* target, const float* pw, int n, int k, int h, int w,
                     const eunet_loss_params* params, const float* sums, const float* gloss, float* glogits,
                     void* stream, const char* what) {
+  EUNET_REQUIRE(logits && target && sums && gloss && glogits && pl_shape_ok(n, k, h, w),
+                "%s: bad args (" PL_SHAPE_RULE ")", what);
   const eunet_loss_params prm = params ? *params : kReferenceParams;
   EUNET_REQUIRE(!pw || prm.focal_norm == 0, "%s: focal_norm = 1 with a pixel weight is not defined", what);
-  const long long total = (long long)n * h * w;
-  const unsigned g = (unsigned)((total + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
-#define LB(KK)                                                                                             \
-  if (pw)                                                                                                  \
-    loss_bwd_kernel<KK, true><<<g, 256, 0, s>>>(logits, target, pw, n, h * w, prm, sums, gloss, glogits);  \
-  else                                                                                                     \
-    loss_bwd_kernel<KK, false><<<g, 256, 0, s>>>(logits, target, nullptr, n, h * w, prm, sums, gloss, glogits);
-  if (k == 1) { LB(1) } else if (k == 2) { LB(2) } else { LB(3) }
-#undef LB
+  by_k(k, [&](auto kc) {
+    by_flag(pw != nullptr, [&](auto wc) {
+      loss_bwd_kernel<decltype(kc)::value, decltype(wc)::value><<<pl_bwd_grid(n, h * w, false), PL_NT, 0, s>>>(
+          logits, target, pw, n, h * w, prm, sums, gloss, glogits);
+    });
+  });
   return eunet::check_launch(what);
 }
 }  // namespace
@@ -322,17 +281,13 @@ extern "C" {
 
 int eunet_loss_fwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
                    const eunet_loss_params* params, float* sums, float* loss, float* parts, void* ws, void* stream) {
-  EUNET_REQUIRE(logits && target && sums && loss && ws && n > 0 && n <= 64 && k >= 1 && k <= 3,
-                "loss_fwd: bad args (N <= 64, K <= 3)");
   return loss_fwd_launch(logits, target, nullptr, n, k, h, w, params, sums, loss, parts, ws, stream, "loss_fwd");
 }
 
 int eunet_loss_fwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k, int h, int w,
                      const eunet_loss_params* params, float* sums, float* loss, float* parts, void* ws,
                      void* stream) {
-  EUNET_REQUIRE(logits && target && pixel_weight && sums && loss && ws && n > 0 && n <= 64 && k >= 1 && k <= 3 &&
-                    h > 0 && w > 0,
-                "loss_fwd_w: bad args (N <= 64, K <= 3, pixel_weight non-null)");
+  EUNET_REQUIRE(pixel_weight, "loss_fwd_w: pixel_weight must not be null");
   return loss_fwd_launch(logits, target, pixel_weight, n, k, h, w, params, sums, loss, parts, ws, stream,
                          "loss_fwd_w");
 }
@@ -340,16 +295,13 @@ int eunet_loss_fwd_w(const float* logits, const int64_t* target, const float* pi
 int eunet_loss_bwd(const float* logits, const int64_t* target, int n, int k, int h, int w,
                    const eunet_loss_params* params, const float* sums, const float* gloss, float* glogits,
                    void* stream) {
-  EUNET_REQUIRE(logits && target && sums && gloss && glogits && n > 0 && k >= 1 && k <= 3, "loss_bwd: bad args");
   return loss_bwd_launch(logits, target, nullptr, n, k, h, w, params, sums, gloss, glogits, stream, "loss_bwd");
 }
 
 int eunet_loss_bwd_w(const float* logits, const int64_t* target, const float* pixel_weight, int n, int k, int h, int w,
                      const eunet_loss_params* params, const float* sums, const float* gloss, float* glogits,
                      void* stream) {
-  EUNET_REQUIRE(logits && target && pixel_weight && sums && gloss && glogits && n > 0 && k >= 1 && k <= 3 && h > 0 &&
-                    w > 0,
-                "loss_bwd_w: bad args (pixel_weight non-null)");
+  EUNET_REQUIRE(pixel_weight, "loss_bwd_w: pixel_weight must not be null");
   return loss_bwd_launch(logits, target, pixel_weight, n, k, h, w, params, sums, gloss, glogits, stream,
                          "loss_bwd_w");
 }

@@ -18,12 +18,11 @@
 
 #include "common.h"
 #include "labelmap.h"
+#include "pixelloss.h"
 
 EUNET_DEBUG_UNIT(sdf)
 
 namespace {
-constexpr int NT = 256;
-constexpr int LPIX = 1024;  // pixels per partial tile: 4 per thread
 constexpr int32_t NONE = EUNET_EDT_NONE;
 
 typedef long long i64x2 __attribute__((ext_vector_type(2)));
@@ -33,9 +32,9 @@ struct Weights {
   float w[3];
 };
 
-__global__ __launch_bounds__(NT) void remap_fg_kernel(const int64_t* target, long long total, long long ign,
+__global__ __launch_bounds__(PL_NT) void remap_fg_kernel(const int64_t* target, long long total, long long ign,
                                                       int64_t* out) {
-  for (long long id = (long long)blockIdx.x * NT + threadIdx.x; id < total; id += (long long)gridDim.x * NT) {
+  for (long long id = (long long)blockIdx.x * PL_NT + threadIdx.x; id < total; id += (long long)gridDim.x * PL_NT) {
     const long long t = (long long)target[id];
     out[id] = (t >= 1 && t != ign) ? 1 : 0;
   }
@@ -56,14 +55,14 @@ __device__ __forceinline__ float phi_of(long long t, int c, bool live, int32_t d
   return (float)(scale * v);
 }
 
-// grid (ceil(HW / (NT * PER)), N).  dout / din: int32 [N][K][HW]
+// grid (ceil(HW / (PL_NT * PER)), N).  dout / din: int32 [N][K][HW]
 template <int K, bool VEC>
-__global__ __launch_bounds__(NT) void sdf_combine_kernel(const int32_t* dout, const int32_t* din,
+__global__ __launch_bounds__(PL_NT) void sdf_combine_kernel(const int32_t* dout, const int32_t* din,
                                                          const int64_t* target, int HW, long long ign, double clip,
                                                          double scale, float* out) {
   constexpr int PER = VEC ? 4 : 1;
   const int n = blockIdx.y;
-  const long long p = ((long long)blockIdx.x * NT + threadIdx.x) * PER;
+  const long long p = ((long long)blockIdx.x * PL_NT + threadIdx.x) * PER;
   if (p >= HW) return;
   EUNET_DASSERT(p + PER <= HW);
   const int32_t* po = dout + (long long)n * K * HW;
@@ -96,32 +95,6 @@ __global__ __launch_bounds__(NT) void sdf_combine_kernel(const int32_t* dout, co
 }
 
 // ---- boundary loss ----------------------------------------------------------------------------------------
-// sig(x), sig(-x) from one exp: no overflow and no cancellation at +-100 (bce_dice.hip's sigmoid_terms)
-__device__ __forceinline__ void sigmoid_pair(float x, float& p, float& q) {
-  const float e = expf(-fabsf(x));
-  const float r = 1.f / (1.f + e);
-  const float hi = r, lo = e * r;
-  p = x >= 0.f ? hi : lo;
-  q = x >= 0.f ? lo : hi;
-}
-
-// the max-subtracted softmax of one pixel
-template <int K>
-__device__ __forceinline__ void softmax_px(const float (&x)[K], float (&p)[K]) {
-  float m = x[0];
-#pragma unroll
-  for (int c = 1; c < K; ++c) m = fmaxf(m, x[c]);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < K; ++c) {
-    p[c] = expf(x[c] - m);
-    s += p[c];
-  }
-  const float inv = 1.f / s;
-#pragma unroll
-  for (int c = 0; c < K; ++c) p[c] *= inv;
-}
-
 // sum_c w_c p_c dist_c of one pixel
 template <int K, bool SOFTMAX>
 __device__ __forceinline__ float fwd_px(const float (&x)[K], const float (&d)[K], const Weights& cw) {
@@ -130,10 +103,7 @@ __device__ __forceinline__ float fwd_px(const float (&x)[K], const float (&d)[K]
     softmax_px<K>(x, p);
   } else {
 #pragma unroll
-    for (int c = 0; c < K; ++c) {
-      float q;
-      sigmoid_pair(x[c], p[c], q);
-    }
+    for (int c = 0; c < K; ++c) p[c] = sigmoid_terms<false>(x[c]).p;
   }
   float v = 0.f;
 #pragma unroll
@@ -142,74 +112,46 @@ __device__ __forceinline__ float fwd_px(const float (&x)[K], const float (&d)[K]
 }
 
 template <int K, bool SOFTMAX, bool VEC>
-__global__ __launch_bounds__(NT) void bl_fwd_kernel(const float* logits, const float* dist, int HW, Weights cw,
-                                                    float* part) {
-  __shared__ float red[4];
-  const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+__global__ __launch_bounds__(PL_NT) void bl_fwd_kernel(const float* logits, const float* dist, int HW, Weights cw,
+                                                       float* part) {
+  const int n = blockIdx.y;
   const float* lg = logits + (long long)n * K * HW;
   const float* dg = dist + (long long)n * K * HW;
-  float acc = 0.f;
-  const int p0 = blockIdx.x * LPIX;
-  const int p1 = min(HW, p0 + LPIX);
-  if (VEC) {  // HW % 4 == 0: every plane and every 4-pixel group starts on 16 bytes
-    const int p = p0 + tid * 4;
-    if (p < p1) {
-      EUNET_DASSERT(p + 3 < HW);
+  float acc[1] = {0.f};
+  pl_tile_visit<VEC>(HW, [&](int p) {
+    float x[K], d[K];
+    if constexpr (VEC) {
       f32x4 xv[K], dv[K];
-#pragma unroll
-      for (int c = 0; c < K; ++c) {
-        xv[c] = *reinterpret_cast<const f32x4*>(lg + (long long)c * HW + p);
-        dv[c] = *reinterpret_cast<const f32x4*>(dg + (long long)c * HW + p);
-      }
+      pl_load4<K>(lg, HW, xv, p);
+      pl_load4<K>(dg, HW, dv, p);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float x[K], d[K];
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-          x[c] = xv[c][j];
-          d[c] = dv[c][j];
-        }
-        acc += fwd_px<K, SOFTMAX>(x, d, cw);
+        pl_px<K>(xv, j, x);
+        pl_px<K>(dv, j, d);
+        acc[0] += fwd_px<K, SOFTMAX>(x, d, cw);
       }
+    } else {
+      pl_load<K>(lg, HW, x, p);
+      pl_load<K>(dg, HW, d, p);
+      acc[0] += fwd_px<K, SOFTMAX>(x, d, cw);
     }
-  } else {
-    for (int p = p0 + tid; p < p1; p += NT) {
-      EUNET_DASSERT(p < HW);
-      float x[K], d[K];
-#pragma unroll
-      for (int c = 0; c < K; ++c) {
-        x[c] = lg[(long long)c * HW + p];
-        d[c] = dg[(long long)c * HW + p];
-      }
-      acc += fwd_px<K, SOFTMAX>(x, d, cw);
-    }
-  }
-  const float s = wave_sum(acc);
-  if (lane == 0) red[wv] = s;
-  __syncthreads();
-  if (tid == 0) part[(long long)n * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  });
+  pl_block_row<1>(acc, part);
 }
 
-// One 256-thread block: per sample, the threads stride over the tile partials (fp64), a fixed-order LDS tree
-// combines them (deterministic); the batch sum is taken in sample order.  den = H W Kw.
+// One 256-thread block: each sample's sum over its tiles (pl_sample_sum); the batch sum is taken in sample order.
+// den = H W Kw.
 __global__ __launch_bounds__(256) void bl_finalize_kernel(const float* part, int tiles, int N, double den,
                                                           float* loss, float* parts) {
-  __shared__ double red[256];
   __shared__ double tot[64];
   const int tid = threadIdx.x;
   EUNET_DASSERT(N <= 64);
   for (int n = 0; n < N; ++n) {
-    double v = 0.0;
-    for (int t = tid; t < tiles; t += 256) v += (double)part[(long long)n * tiles + t];
-    red[tid] = v;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if (tid < off) red[tid] += red[tid + off];
-      __syncthreads();
-    }
+    double v[1];
+    pl_sample_sum<1>(part, tiles, n, v);
     if (tid == 0) {
-      tot[n] = red[0];
-      if (parts) parts[n] = (float)(red[0] / den);
+      tot[n] = v[0];
+      if (parts) parts[n] = (float)(v[0] / den);
     }
     __syncthreads();
   }
@@ -241,69 +183,51 @@ __device__ __forceinline__ void bwd_px(const float (&x)[K], const float (&d)[K],
   } else {
 #pragma unroll
     for (int c = 0; c < K; ++c) {
-      float p, q;
-      sigmoid_pair(x[c], p, q);
-      g[c] = cw.w[c] * d[c] * (p * q);
+      const Sig s = sigmoid_terms<false>(x[c]);
+      g[c] = cw.w[c] * d[c] * (s.p * s.q);
     }
   }
 }
 
 // VEC: one thread per group of 4 pixels (HW % 4 == 0, so a group never straddles two samples).  inv = 1 / (N H W Kw)
 template <int K, bool SOFTMAX, bool VEC>
-__global__ __launch_bounds__(NT) void bl_bwd_kernel(const float* logits, const float* dist, int N, int HW, Weights cw,
-                                                    float inv, const float* gloss, float* glog) {
+__global__ __launch_bounds__(PL_NT) void bl_bwd_kernel(const float* logits, const float* dist, int N, int HW,
+                                                       Weights cw, float inv, const float* gloss, float* glog) {
   constexpr int PER = VEC ? 4 : 1;
-  const long long id = ((long long)blockIdx.x * NT + threadIdx.x) * PER;
-  const long long total = (long long)N * HW;
-  if (id >= total) return;
-  EUNET_DASSERT(id + PER <= total);
-  const int n = (int)(id / HW);
-  const int p = (int)(id - (long long)n * HW);
-  EUNET_DASSERT(n < N && p + PER <= HW);
-  const float* lg = logits + (long long)n * K * HW + p;
-  const float* dg = dist + (long long)n * K * HW + p;
-  float* gl = glog + (long long)n * K * HW + p;
+  long long id;
+  int n, p;
+  if (!pl_bwd_split<PER>(N, HW, id, n, p)) return;
+  const long long at = (long long)n * K * HW + p;
   const float g0 = gloss[0] * inv;
-  if (VEC) {
+  float x[K], d[K], g[K];
+  if constexpr (VEC) {
     f32x4 xv[K], dv[K], gv[K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) {
-      xv[c] = *reinterpret_cast<const f32x4*>(lg + (long long)c * HW);
-      dv[c] = *reinterpret_cast<const f32x4*>(dg + (long long)c * HW);
-    }
+    pl_load4<K>(logits + at, HW, xv);
+    pl_load4<K>(dist + at, HW, dv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float x[K], d[K], g[K];
-#pragma unroll
-      for (int c = 0; c < K; ++c) {
-        x[c] = xv[c][j];
-        d[c] = dv[c][j];
-      }
+      pl_px<K>(xv, j, x);
+      pl_px<K>(dv, j, d);
       bwd_px<K, SOFTMAX>(x, d, cw, g);
 #pragma unroll
       for (int c = 0; c < K; ++c) gv[c][j] = g0 * g[c];
     }
-#pragma unroll
-    for (int c = 0; c < K; ++c) *reinterpret_cast<f32x4*>(gl + (long long)c * HW) = gv[c];
+    pl_store4<K>(glog + at, HW, gv);
   } else {
-    float x[K], d[K], g[K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) {
-      x[c] = lg[(long long)c * HW];
-      d[c] = dg[(long long)c * HW];
-    }
+    pl_load<K>(logits + at, HW, x);
+    pl_load<K>(dist + at, HW, d);
     bwd_px<K, SOFTMAX>(x, d, cw, g);
 #pragma unroll
-    for (int c = 0; c < K; ++c) gl[(long long)c * HW] = g0 * g[c];
+    for (int c = 0; c < K; ++c) g[c] = g0 * g[c];
+    pl_store<K>(glog + at, HW, g);
   }
 }
 
 // the shared argument rules of the two loss entries; fills cw and Kw
 bool loss_args(const char* what, const void* a, const void* b, const void* c, const void* d, int n, int k, int h,
                int w, int activation, const float* class_weight, Weights* cw, int* kw) {
-  if (!(a && b && c && d && n > 0 && n <= 64 && k >= 1 && k <= 3 && h > 0 && w > 0 &&
-        (long long)h * w < (1ll << 31) - LPIX)) {
-    eunet::set_error("%s: bad args (N <= 64, K <= 3)", what);
+  if (!(a && b && c && d && pl_shape_ok(n, k, h, w))) {
+    eunet::set_error("%s: bad args (" PL_SHAPE_RULE ")", what);
     return false;
   }
   if (activation != EUNET_BOUNDARY_SOFTMAX && activation != EUNET_BOUNDARY_SIGMOID) {
@@ -325,6 +249,16 @@ bool loss_args(const char* what, const void* a, const void* b, const void* c, co
   }
   if (*kw < 1) *kw = 1;
   return true;
+}
+
+// f(K, SOFTMAX) for the (k, activation) that loss_args let through: no softmax kernel of K = 1 is built
+template <class F>
+void by_k_softmax(int k, int activation, F&& f) {
+  by_k(k, [&](auto kc) {
+    by_flag(activation == EUNET_BOUNDARY_SOFTMAX, [&](auto sc) {
+      if constexpr (decltype(kc)::value > 1 || !decltype(sc)::value) f(kc, sc);
+    });
+  });
 }
 
 }  // namespace
@@ -362,8 +296,7 @@ int eunet_signed_distance(const int64_t* target, int n, int k, int h, int w, int
   if (k == 1) {
     int64_t* fg = (int64_t*)(ws + 2 * planes);
     const long long total = (long long)n * HW;
-    const long long b = (total + NT - 1) / NT;
-    remap_fg_kernel<<<(unsigned)(b < 2048 ? b : 2048), NT, 0, s>>>(target, total, ign, fg);
+    remap_fg_kernel<<<grid_for(total, 2048), PL_NT, 0, s>>>(target, total, ign, fg);
     EUNET_LAUNCH_CHECK("signed_distance");
     sites = fg;
     values[0] = 1;
@@ -372,21 +305,21 @@ int eunet_signed_distance(const int64_t* target, int n, int k, int h, int w, int
   if (rc != EUNET_OK) return rc;
   rc = eunet_edt_sq(sites, n, h, w, values, k, EUNET_EDT_NE, din, stream);
   if (rc != EUNET_OK) return rc;
-  const bool vec = HW % 4 == 0 && ((uintptr_t)target % 16 == 0) && ((uintptr_t)ws % 16 == 0) &&
-                   ((uintptr_t)out % 16 == 0);
-  const dim3 grid((unsigned)cdiv(HW, NT * (vec ? 4 : 1)), (unsigned)n);
+  const bool vec = pl_vec_ok(HW, {target, ws, out});
+  const dim3 grid((unsigned)cdiv(HW, PL_NT * (vec ? 4 : 1)), (unsigned)n);
   const double cl = (double)clip, sc = (double)scale;
-#define SK(KK)                                                                                          \
-  if (vec) sdf_combine_kernel<KK, true><<<grid, NT, 0, s>>>(dout, din, target, HW, ign, cl, sc, out);   \
-  else sdf_combine_kernel<KK, false><<<grid, NT, 0, s>>>(dout, din, target, HW, ign, cl, sc, out);
-  if (k == 1) { SK(1) } else if (k == 2) { SK(2) } else { SK(3) }
-#undef SK
+  by_k(k, [&](auto kc) {
+    by_flag(vec, [&](auto vc) {
+      sdf_combine_kernel<decltype(kc)::value, decltype(vc)::value>
+          <<<grid, PL_NT, 0, s>>>(dout, din, target, HW, ign, cl, sc, out);
+    });
+  });
   return eunet::check_launch("signed_distance");
 }
 
 int eunet_boundary_loss_workspace_bytes(int n, int h, int w, size_t* bytes) {
   EUNET_REQUIRE(bytes && n > 0 && h > 0 && w > 0, "boundary_loss_workspace_bytes: bad args");
-  *bytes = (size_t)n * cdiv(h * w, LPIX) * sizeof(float);
+  *bytes = pl_workspace_bytes(n, h, w, 1);
   return EUNET_OK;
 }
 
@@ -396,19 +329,15 @@ int eunet_boundary_loss_fwd(const float* logits, const float* dist, int n, int k
   int kw;
   if (!loss_args("boundary_loss_fwd", logits, dist, loss, ws, n, k, h, w, activation, class_weight, &cw, &kw))
     return EUNET_ERR_INVALID;
-  const int HW = h * w, tiles = cdiv(HW, LPIX);
+  const int HW = h * w, tiles = pl_tiles(HW);
   const hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(tiles, n);
-  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)dist % 16 == 0);
-  const bool sm = activation == EUNET_BOUNDARY_SOFTMAX;
   float* part = (float*)ws;
-#define BK(KK, SS)                                                                           \
-  if (vec) bl_fwd_kernel<KK, SS, true><<<grid, NT, 0, s>>>(logits, dist, HW, cw, part);      \
-  else bl_fwd_kernel<KK, SS, false><<<grid, NT, 0, s>>>(logits, dist, HW, cw, part);
-  if (k == 1) { BK(1, false) }
-  else if (k == 2) { if (sm) { BK(2, true) } else { BK(2, false) } }
-  else { if (sm) { BK(3, true) } else { BK(3, false) } }
-#undef BK
+  by_k_softmax(k, activation, [&](auto kc, auto sc) {
+    by_flag(pl_vec_ok(HW, {logits, dist}), [&](auto vc) {
+      bl_fwd_kernel<decltype(kc)::value, decltype(sc)::value, decltype(vc)::value>
+          <<<dim3(tiles, n), PL_NT, 0, s>>>(logits, dist, HW, cw, part);
+    });
+  });
   bl_finalize_kernel<<<1, 256, 0, s>>>(part, tiles, n, (double)HW * kw, loss, parts);
   return eunet::check_launch("boundary_loss_fwd");
 }
@@ -420,20 +349,15 @@ int eunet_boundary_loss_bwd(const float* logits, const float* dist, int n, int k
   if (!loss_args("boundary_loss_bwd", logits, dist, gloss, glogits, n, k, h, w, activation, class_weight, &cw, &kw))
     return EUNET_ERR_INVALID;
   const int HW = h * w;
-  const bool vec = HW % 4 == 0 && ((uintptr_t)logits % 16 == 0) && ((uintptr_t)dist % 16 == 0) &&
-                   ((uintptr_t)glogits % 16 == 0);
-  const long long threads = (long long)n * HW / (vec ? 4 : 1);
-  const unsigned g = (unsigned)((threads + NT - 1) / NT);
+  const bool vec = pl_vec_ok(HW, {logits, dist, glogits});
   const hipStream_t s = (hipStream_t)stream;
-  const bool sm = activation == EUNET_BOUNDARY_SOFTMAX;
   const float inv = (float)(1.0 / ((double)n * HW * kw));
-#define BK(KK, SS)                                                                                      \
-  if (vec) bl_bwd_kernel<KK, SS, true><<<g, NT, 0, s>>>(logits, dist, n, HW, cw, inv, gloss, glogits);  \
-  else bl_bwd_kernel<KK, SS, false><<<g, NT, 0, s>>>(logits, dist, n, HW, cw, inv, gloss, glogits);
-  if (k == 1) { BK(1, false) }
-  else if (k == 2) { if (sm) { BK(2, true) } else { BK(2, false) } }
-  else { if (sm) { BK(3, true) } else { BK(3, false) } }
-#undef BK
+  by_k_softmax(k, activation, [&](auto kc, auto sc) {
+    by_flag(vec, [&](auto vc) {
+      bl_bwd_kernel<decltype(kc)::value, decltype(sc)::value, decltype(vc)::value>
+          <<<pl_bwd_grid(n, HW, vec), PL_NT, 0, s>>>(logits, dist, n, HW, cw, inv, gloss, glogits);
+    });
+  });
   return eunet::check_launch("boundary_loss_bwd");
 }
 

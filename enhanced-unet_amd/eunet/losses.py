@@ -144,33 +144,19 @@ def check_targets():
                          f"(F.cross_entropy would raise: class index out of bounds)")
 
 
-class CombinedLossFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, params, track_targets):
-        logits = logits.contiguous().float()
-        target = target.contiguous().long()
-        n, k, h, w = logits.shape
-        if target.shape != (n, h, w):
-            raise ValueError(f"target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
-        dev = logits.device
-        sums = torch.empty(ops.loss_sums_len(n, k), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        parts = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        ws = torch.empty(ops.loss_workspace_bytes(n, k, h, w), dtype=torch.uint8, device=dev)
-        ops.loss_fwd(logits, target, params, sums, loss, parts, ws)
-        if track_targets:
-            _record_bad(sums)
-        ctx.save_for_backward(logits, target, sums)
-        ctx.params = params
-        ctx.mark_non_differentiable(parts)
-        return loss, parts
+def _check_logits_target(what: str, logits, target=None):
+    """The shape rules every per-pixel loss shares, as ValueError: [N, K, H, W] logits and a target of [N, H, W]."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
+        raise ValueError(f"{what}: expected [N, K, H, W] logits, got "
+                         f"{tuple(logits.shape) if isinstance(logits, torch.Tensor) else type(logits).__name__}")
+    if target is not None and target.shape != logits.shape[:1] + logits.shape[2:]:
+        raise ValueError(f"{what}: target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
 
-    @staticmethod
-    def backward(ctx, gloss, gparts):
-        logits, target, sums = ctx.saved_tensors
-        glog = torch.empty_like(logits)
-        ops.loss_bwd(logits, target, ctx.params, sums, gloss.contiguous().float().reshape(1), glog)
-        return glog, None, None, None
+
+def _check_on_device(what: str, *tensors):
+    """The device rule, as EunetError (there is no CPU fallback); it comes after every ValueError rule of a loss."""
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.EunetError(f"{what} needs device tensors (no CPU fallback)")
 
 
 def _check_pixel_weight(pixel_weight, logits, target, what: str):
@@ -191,35 +177,58 @@ def _check_pixel_weight(pixel_weight, logits, target, what: str):
         raise ValueError(f"{what}: pixel_weight must be contiguous")
 
 
-class WeightedCombinedLossFunction(torch.autograd.Function):
-    """CombinedLossFunction with the focal summand multiplied by a per-pixel weight (eunet_loss_fwd_w)."""
+class _SumsLossFunction(torch.autograd.Function):
+    """A loss whose forward saves per-sample sums for an analytic backward (loss, bce_dice): apply(logits, target,
+    params, track_targets, pixel_weight=None).  pixel_weight None runs the unweighted entry points, a tensor the
+    _w ones.  Subclasses name the loss, the columns of parts and the six ops."""
+    what = n_parts = sums_len = workspace_bytes = fwd = bwd = fwd_w = bwd_w = None
 
-    @staticmethod
-    def forward(ctx, logits, target, pixel_weight, params, track_targets):
+    @classmethod
+    def check(cls, logits, params):
+        pass
+
+    @classmethod
+    def forward(cls, ctx, logits, target, params, track_targets, pixel_weight=None):
         logits = logits.contiguous().float()
         target = target.contiguous().long()
+        _check_logits_target(cls.what, logits, target)
+        cls.check(logits, params)
+        _check_on_device(cls.what, logits, target)
         n, k, h, w = logits.shape
-        if target.shape != (n, h, w):
-            raise ValueError(f"target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
         dev = logits.device
-        sums = torch.empty(ops.loss_sums_len(n, k), dtype=torch.float32, device=dev)
+        sums = torch.empty(cls.sums_len(n, k), dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        parts = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        ws = torch.empty(ops.loss_workspace_bytes(n, k, h, w), dtype=torch.uint8, device=dev)
-        ops.loss_fwd_w(logits, target, pixel_weight, params, sums, loss, parts, ws)
+        parts = torch.empty(n, cls.n_parts, dtype=torch.float32, device=dev)
+        ws = torch.empty(cls.workspace_bytes(n, k, h, w), dtype=torch.uint8, device=dev)
+        if pixel_weight is None:
+            cls.fwd(logits, target, params, sums, loss, parts, ws)
+        else:
+            cls.fwd_w(logits, target, pixel_weight, params, sums, loss, parts, ws)
         if track_targets:
             _record_bad(sums)
-        ctx.save_for_backward(logits, target, pixel_weight, sums)
+        ctx.save_for_backward(logits, target, sums, *([] if pixel_weight is None else [pixel_weight]))
         ctx.params = params
         ctx.mark_non_differentiable(parts)
         return loss, parts
 
-    @staticmethod
-    def backward(ctx, gloss, gparts):
-        logits, target, pixel_weight, sums = ctx.saved_tensors
+    @classmethod
+    def backward(cls, ctx, gloss, gparts):
+        logits, target, sums, *pw = ctx.saved_tensors
         glog = torch.empty_like(logits)
-        ops.loss_bwd_w(logits, target, pixel_weight, ctx.params, sums, gloss.contiguous().float().reshape(1), glog)
+        gloss = gloss.contiguous().float().reshape(1)
+        if pw:
+            cls.bwd_w(logits, target, pw[0], ctx.params, sums, gloss, glog)
+        else:
+            cls.bwd(logits, target, ctx.params, sums, gloss, glog)
         return glog, None, None, None, None
+
+
+class CombinedLossFunction(_SumsLossFunction):
+    """Focal + Dice + Tversky (eunet_loss_fwd / _bwd, with a pixel_weight eunet_loss_fwd_w / _bwd_w)."""
+    what, n_parts = "combined_loss", 3
+    sums_len, workspace_bytes = staticmethod(ops.loss_sums_len), staticmethod(ops.loss_workspace_bytes)
+    fwd, bwd = staticmethod(ops.loss_fwd), staticmethod(ops.loss_bwd)
+    fwd_w, bwd_w = staticmethod(ops.loss_fwd_w), staticmethod(ops.loss_bwd_w)
 
 
 class ConsistencyFunction(torch.autograd.Function):
@@ -258,14 +267,12 @@ def combined_loss(logits: torch.Tensor, target: torch.Tensor, return_parts: bool
     ops.border_weight_map): multiplies the per-pixel focal summand, the pixel mean keeps its N*H*W
     denominator, Dice and Tversky are untouched; it takes no gradient and cannot be combined with
     focal_norm = 1."""
-    if pixel_weight is None:
-        loss, parts = CombinedLossFunction.apply(logits, target, params, track_targets)
-    else:
+    if pixel_weight is not None:
         _check_pixel_weight(pixel_weight, logits, target, "combined_loss")
         if params is not None and params.focal_norm != 0:
             raise ValueError("combined_loss: focal_norm = 1 with a pixel_weight is not defined (its denominator "
                              "would need a definition of its own)")
-        loss, parts = WeightedCombinedLossFunction.apply(logits, target, pixel_weight, params, track_targets)
+    loss, parts = CombinedLossFunction.apply(logits, target, params, track_targets, pixel_weight)
     if validate:
         check_targets()
     return (loss, parts) if return_parts else loss
@@ -307,70 +314,16 @@ def check_bce_dice_mode(params: Optional[BCEDiceParams], k: int):
         raise ValueError("K = 1 has the target mode 'foreground' only")
 
 
-class BCEDiceFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, params, track_targets):
-        logits = logits.contiguous().float()
-        target = target.contiguous().long()
-        if logits.dim() != 4:
-            raise ValueError(f"expected [N, K, H, W] logits, got {tuple(logits.shape)}")
-        n, k, h, w = logits.shape
-        if target.shape != (n, h, w):
-            raise ValueError(f"target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
-        check_bce_dice_mode(params, k)
-        if not logits.is_cuda or not target.is_cuda:
-            raise _lib.EunetError("bce_dice_loss needs device tensors (no CPU fallback)")
-        dev = logits.device
-        sums = torch.empty(ops.bce_dice_sums_len(n, k), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        parts = torch.empty(n, 2, dtype=torch.float32, device=dev)
-        ws = torch.empty(ops.bce_dice_workspace_bytes(n, k, h, w), dtype=torch.uint8, device=dev)
-        ops.bce_dice_fwd(logits, target, params, sums, loss, parts, ws)
-        if track_targets:
-            _record_bad(sums)
-        ctx.save_for_backward(logits, target, sums)
-        ctx.params = params
-        ctx.mark_non_differentiable(parts)
-        return loss, parts
+class BCEDiceFunction(_SumsLossFunction):
+    """Sigmoid BCE + soft Dice (eunet_bce_dice_fwd / _bwd, with a pixel_weight eunet_bce_dice_fwd_w / _bwd_w)."""
+    what, n_parts = "bce_dice_loss", 2
+    sums_len, workspace_bytes = staticmethod(ops.bce_dice_sums_len), staticmethod(ops.bce_dice_workspace_bytes)
+    fwd, bwd = staticmethod(ops.bce_dice_fwd), staticmethod(ops.bce_dice_bwd)
+    fwd_w, bwd_w = staticmethod(ops.bce_dice_fwd_w), staticmethod(ops.bce_dice_bwd_w)
 
-    @staticmethod
-    def backward(ctx, gloss, gparts):
-        logits, target, sums = ctx.saved_tensors
-        glog = torch.empty_like(logits)
-        ops.bce_dice_bwd(logits, target, ctx.params, sums, gloss.contiguous().float().reshape(1), glog)
-        return glog, None, None, None
-
-
-class WeightedBCEDiceFunction(torch.autograd.Function):
-    """BCEDiceFunction with bce(x,t)_c multiplied by a per-pixel weight (eunet_bce_dice_fwd_w)."""
-
-    @staticmethod
-    def forward(ctx, logits, target, pixel_weight, params, track_targets):
-        logits = logits.contiguous().float()
-        target = target.contiguous().long()
-        n, k, h, w = logits.shape
-        check_bce_dice_mode(params, k)
-        if not logits.is_cuda or not target.is_cuda:
-            raise _lib.EunetError("bce_dice_loss needs device tensors (no CPU fallback)")
-        dev = logits.device
-        sums = torch.empty(ops.bce_dice_sums_len(n, k), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        parts = torch.empty(n, 2, dtype=torch.float32, device=dev)
-        ws = torch.empty(ops.bce_dice_workspace_bytes(n, k, h, w), dtype=torch.uint8, device=dev)
-        ops.bce_dice_fwd_w(logits, target, pixel_weight, params, sums, loss, parts, ws)
-        if track_targets:
-            _record_bad(sums)
-        ctx.save_for_backward(logits, target, pixel_weight, sums)
-        ctx.params = params
-        ctx.mark_non_differentiable(parts)
-        return loss, parts
-
-    @staticmethod
-    def backward(ctx, gloss, gparts):
-        logits, target, pixel_weight, sums = ctx.saved_tensors
-        glog = torch.empty_like(logits)
-        ops.bce_dice_bwd_w(logits, target, pixel_weight, ctx.params, sums, gloss.contiguous().float().reshape(1), glog)
-        return glog, None, None, None, None
+    @classmethod
+    def check(cls, logits, params):
+        check_bce_dice_mode(params, logits.shape[1])
 
 
 def bce_dice_loss(logits: torch.Tensor, target: torch.Tensor, return_parts: bool = False,
@@ -381,15 +334,9 @@ def bce_dice_loss(logits: torch.Tensor, target: torch.Tensor, return_parts: bool
     (bce_n, dice_n).  Pixels at ignore_index count nowhere; other invalid targets count nowhere either
     and are reported by check_targets() (at once with validate=True).  pixel_weight (float32 [N,H,W]) multiplies
     bce(x,t)_c in BCE and bce_n; the denominators and the Dice terms are untouched and it takes no gradient."""
-    if pixel_weight is None:
-        loss, parts = BCEDiceFunction.apply(logits, target, params, track_targets)
-    else:
-        if logits.dim() != 4:
-            raise ValueError(f"expected [N, K, H, W] logits, got {tuple(logits.shape)}")
-        if target.shape != logits.shape[:1] + logits.shape[2:]:
-            raise ValueError(f"target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+    if pixel_weight is not None:
         _check_pixel_weight(pixel_weight, logits, target, "bce_dice_loss")
-        loss, parts = WeightedBCEDiceFunction.apply(logits, target, pixel_weight, params, track_targets)
+    loss, parts = BCEDiceFunction.apply(logits, target, params, track_targets, pixel_weight)
     if validate:
         check_targets()
     return (loss, parts) if return_parts else loss
@@ -433,9 +380,7 @@ def _check_boundary_args(logits, dist, activation, class_weight, what: str):
     """The rules of boundary_loss that need no device, raised as ValueError; returns the K class weights."""
     if activation not in ops.BOUNDARY_ACTIVATIONS:
         raise ValueError(f"{what}: activation must be 'softmax' or 'sigmoid', not {activation!r}")
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
-        raise ValueError(f"{what}: expected [N, K, H, W] logits, got "
-                         f"{tuple(logits.shape) if isinstance(logits, torch.Tensor) else type(logits).__name__}")
+    _check_logits_target(what, logits)
     if not logits.is_floating_point():
         raise ValueError(f"{what}: logits must be floating point, got {logits.dtype}")
     k = logits.shape[1]
@@ -467,8 +412,8 @@ class BoundaryLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, dist, activation, cw):
         logits = logits.contiguous().float()
-        if not logits.is_cuda:
-            raise _lib.EunetError("boundary_loss needs device tensors (no CPU fallback)")
+        _check_logits_target("boundary_loss", logits)
+        _check_on_device("boundary_loss", logits)
         n, k, h, w = logits.shape
         dev = logits.device
         loss = torch.empty((), dtype=torch.float32, device=dev)

@@ -28,22 +28,23 @@ _LIB = torch.library.Library("eunet", "DEF")
 DISPATCHED: dict = {}
 
 
-def _dispatched(kinds: str, returns_tensor: bool = False):
+def _dispatched(kinds: str, returns_tensor: bool = False, names=None):
     """kinds: one token per parameter -- A (Act), T (tensor), i (int), I (list of int), f (float), b (bool),
-    d (torch dtype), s (str); A! / T! mark the arguments the op writes, a trailing ? an optional (None-able) argument."""
+    d (torch dtype), s (str); A! / T! mark the arguments the op writes, a trailing ? an optional (None-able) argument.
+    names: the parameter names of a function that takes *args (no defaults); otherwise read from its signature."""
     import inspect
     import string
 
     ks = kinds.split()
 
     def deco(fn):
-        sig = inspect.signature(fn)
-        names = list(sig.parameters)
-        if len(names) != len(ks):
-            raise _lib.EunetError(f"_dispatched({fn.__name__}): {len(names)} parameters, {len(ks)} kinds")
+        params = [] if names else list(inspect.signature(fn).parameters.values())
+        argnames = list(names or (p.name for p in params))
+        if len(argnames) != len(ks):
+            raise _lib.EunetError(f"_dispatched({fn.__name__}): {len(argnames)} parameters, {len(ks)} kinds")
         letters = iter(string.ascii_lowercase)
         parts = []
-        for nm, k in zip(names, ks):
+        for nm, k in zip(argnames, ks):
             q = "?" if k.endswith("?") else ""
             base = k.rstrip("?")
             w = base.endswith("!")
@@ -72,8 +73,8 @@ def _dispatched(kinds: str, returns_tensor: bool = False):
         _LIB.impl(fn.__name__, impl, "CPU")  # raises EunetError in _ptr / act: no CPU fallback
         op = getattr(torch.ops.eunet, fn.__name__)
 
-        defaults = [p.default for p in sig.parameters.values()]
-        index = {nm: i for i, nm in enumerate(names)}
+        defaults = [p.default for p in params]
+        index = {nm: i for i, nm in enumerate(argnames)}
         isact = [k.startswith("A") for k in ks]
 
         def wrapper(*args, **kwargs):
@@ -441,52 +442,68 @@ def bce_dice_workspace_bytes(n, k, h, w):
     return b.value
 
 
+# eunet_bce_dice_params as the dispatcher schema spells it: (struct field, kind, schema names); a table of three
+# floats is three scalars.  The four op schemas, _bce_flat and _bce_struct are derived from this list.
+_BCE_FIELDS = (("pos_weight", "f", ("pw0", "pw1", "pw2")), ("class_weight", "f", ("cw0", "cw1", "cw2")),
+               ("dice_weight", "f", ("dw0", "dw1", "dw2")), ("w_bce", "f", ("w_bce",)), ("w_dice", "f", ("w_dice",)),
+               ("smooth", "f", ("smooth",)), ("ignore_index", "i", ("ignore_index",)),
+               ("target_mode", "i", ("target_mode",)))
+_BCE_NAMES = [nm for _, _, names in _BCE_FIELDS for nm in names]
+_BCE_KINDS = [kind for _, kind, names in _BCE_FIELDS for _ in names]
+
 _bce_defaults = None  # the library's default parameters as _bce_flat gives them, read once
 
 
 def _bce_flat(p):
-    """eunet_bce_dice_params as the 14 scalars of the dispatcher schema (None: the library's defaults)."""
+    """eunet_bce_dice_params as the scalars of the dispatcher schema (None: the library's defaults)."""
     global _bce_defaults
     if p is None:
         if _bce_defaults is None:
             _bce_defaults = _bce_flat(bce_dice_default_params())
         return _bce_defaults
-    return (*p.pos_weight, *p.class_weight, *p.dice_weight, p.w_bce, p.w_dice, p.smooth, p.ignore_index,
-            p.target_mode)
+    flat = []
+    for field, _, names in _BCE_FIELDS:
+        v = getattr(p, field)
+        flat += list(v) if len(names) > 1 else [v]
+    return tuple(flat)
 
 
 def _bce_struct(v):
-    p = _lib.BCEDiceParams()
-    p.pos_weight[:], p.class_weight[:], p.dice_weight[:] = v[0:3], v[3:6], v[6:9]
-    p.w_bce, p.w_dice, p.smooth, p.ignore_index, p.target_mode = v[9], v[10], v[11], v[12], v[13]
+    p, j = _lib.BCEDiceParams(), 0
+    for field, _, names in _BCE_FIELDS:
+        if len(names) > 1:
+            getattr(p, field)[:] = v[j:j + len(names)]
+        else:
+            setattr(p, field, v[j])
+        j += len(names)
     return p
 
 
-@_dispatched("T T f f f f f f f f f f f f i i T! T! T! T!")
-def bce_dice_fwd(logits, target, pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth,
-                 ignore_index, target_mode, sums, loss, parts, ws):
-    n, k, h, w = logits.shape
-    prm = _bce_struct((pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth, ignore_index,
-                       target_mode))
-    call("eunet_bce_dice_fwd", _ptr(logits), _ptr(target), n, k, h, w, ctypes.byref(prm), _ptr(sums), _ptr(loss),
-         _ptr(parts), _ptr(ws), _stream())
+def _bce_op(entry, lead, tail):
+    """Registers torch.ops.eunet.<entry>(*lead, <the parameter scalars>, *tail) over eunet_<entry>(*lead, n, k, h, w,
+    &params, *tail, stream); lead / tail: the tensor arguments as "name:kind" words.  The dispatcher op takes the
+    struct spread over scalars (a float of the struct survives the round trip through the schema's double)."""
+    lead, tail = ([a.split(":") for a in side.split()] for side in (lead, tail))
+
+    def body(*args):
+        tensors, scalars, outs = args[:len(lead)], args[len(lead):-len(tail)], args[-len(tail):]
+        n, k, h, w = tensors[0].shape
+        call("eunet_" + entry, *map(_ptr, tensors), n, k, h, w, ctypes.byref(_bce_struct(scalars)), *map(_ptr, outs),
+             _stream())
+
+    body.__name__ = entry
+    return _dispatched(" ".join([k for _, k in lead] + _BCE_KINDS + [k for _, k in tail]),
+                       names=[nm for nm, _ in lead] + _BCE_NAMES + [nm for nm, _ in tail])(body)
 
 
-@_dispatched("T T f f f f f f f f f f f f i i T T T!")
-def bce_dice_bwd(logits, target, pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth,
-                 ignore_index, target_mode, sums, gloss, glogits):
-    n, k, h, w = logits.shape
-    prm = _bce_struct((pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth, ignore_index,
-                       target_mode))
-    call("eunet_bce_dice_bwd", _ptr(logits), _ptr(target), n, k, h, w, ctypes.byref(prm), _ptr(sums), _ptr(gloss),
-         _ptr(glogits), _stream())
+_FWD, _BWD = "sums:T! loss:T! parts:T! ws:T!", "sums:T gloss:T glogits:T!"
+_bce_dice_fwd_op = _bce_op("bce_dice_fwd", "logits:T target:T", _FWD)
+_bce_dice_bwd_op = _bce_op("bce_dice_bwd", "logits:T target:T", _BWD)
+_bce_dice_fwd_w_op = _bce_op("bce_dice_fwd_w", "logits:T target:T pixel_weight:T", _FWD)
+_bce_dice_bwd_w_op = _bce_op("bce_dice_bwd_w", "logits:T target:T pixel_weight:T", _BWD)
 
 
-# the dispatcher ops take the struct spread over scalars (a float of the struct survives the round trip
-# through the schema's double); the module's functions of the same names take the struct
-_bce_dice_fwd_op, _bce_dice_bwd_op = bce_dice_fwd, bce_dice_bwd
-
-
+# the module's functions of the ops' names take the struct
 def bce_dice_fwd(logits, target, params, sums, loss, parts, ws):
     """torch.ops.eunet.bce_dice_fwd; params: _lib.BCEDiceParams or None (the library's defaults)."""
     _bce_dice_fwd_op(logits, target, *_bce_flat(params), sums, loss, parts, ws)
@@ -495,29 +512,6 @@ def bce_dice_fwd(logits, target, params, sums, loss, parts, ws):
 def bce_dice_bwd(logits, target, params, sums, gloss, glogits):
     """torch.ops.eunet.bce_dice_bwd: glogits = gloss * d loss / d logits from the forward's sums."""
     _bce_dice_bwd_op(logits, target, *_bce_flat(params), sums, gloss, glogits)
-
-
-@_dispatched("T T T f f f f f f f f f f f f i i T! T! T! T!")
-def bce_dice_fwd_w(logits, target, pixel_weight, pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth,
-                   ignore_index, target_mode, sums, loss, parts, ws):
-    n, k, h, w = logits.shape
-    prm = _bce_struct((pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth, ignore_index,
-                       target_mode))
-    call("eunet_bce_dice_fwd_w", _ptr(logits), _ptr(target), _ptr(pixel_weight), n, k, h, w, ctypes.byref(prm),
-         _ptr(sums), _ptr(loss), _ptr(parts), _ptr(ws), _stream())
-
-
-@_dispatched("T T T f f f f f f f f f f f f i i T T T!")
-def bce_dice_bwd_w(logits, target, pixel_weight, pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth,
-                   ignore_index, target_mode, sums, gloss, glogits):
-    n, k, h, w = logits.shape
-    prm = _bce_struct((pw0, pw1, pw2, cw0, cw1, cw2, dw0, dw1, dw2, w_bce, w_dice, smooth, ignore_index,
-                       target_mode))
-    call("eunet_bce_dice_bwd_w", _ptr(logits), _ptr(target), _ptr(pixel_weight), n, k, h, w, ctypes.byref(prm),
-         _ptr(sums), _ptr(gloss), _ptr(glogits), _stream())
-
-
-_bce_dice_fwd_w_op, _bce_dice_bwd_w_op = bce_dice_fwd_w, bce_dice_bwd_w
 
 
 def bce_dice_fwd_w(logits, target, pixel_weight, params, sums, loss, parts, ws):

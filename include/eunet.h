@@ -240,8 +240,16 @@ int eunet_head_bwd(const float* z, int n, int h, int w, int k, const float* w1, 
                    float* gw1, float* gb1, float* ggamma, float* gbeta, float* gw2, float* gb2,
                    int dtype, void* ws, void* stream);
 
+/* ---- per-pixel losses: the shape rule --------------------------------------
+ * Every forward and backward entry point of the three per-pixel losses below (eunet_loss_*, eunet_bce_dice_*,
+ * eunet_boundary_loss_*, the _w variants included) takes logits [N,K,H,W] fp32 NCHW with
+ *   N in 1..64, K in 1..3, H > 0, W > 0 and H*W < 2^31 - 1024,
+ * and returns EUNET_ERR_INVALID for anything else, before any launch (csrc/pixelloss.h, pl_shape_ok).  N <= 64
+ * is the finalize block's per-sample storage; the last bound keeps a plane index plus one tile of 1024 pixels in
+ * an int.  A backward call takes the shape of the forward call whose sums it reads. */
+
 /* ---- combined loss (train_eval.py:28-60, 134-197, 262-337) ----------------
- * logits [N,K,H,W] fp32 NCHW, target [N,H,W] int64; K <= 3.  params (nullable = the
+ * logits [N,K,H,W] fp32 NCHW, target [N,H,W] int64 (the shape rule above).  params (nullable = the
  * Trainer's enhanced_unet configuration, eunet_loss_reference_params):
  *   loss = w_focal * focal + (1/N) sum_n [w_dice dice_n + w_tversky tversky_n]
  *   focal = sum over all pixels of alpha_t (1 - pt)^gamma ce / F_den, ce = -w_t log p_t

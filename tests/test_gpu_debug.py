@@ -2,7 +2,9 @@
 in a child process whose EUNET_LIB points at it, a deliberately failing device check is reported
 (unit and line), and then full training steps of the single- and dual-branch models (bf16 and
 fp32, ragged tile edges, multi-split weight gradients, the LDS-DMA halo staging) trip none of
-the device-side checks on staging offsets, tile / split indices and output addresses."""
+the device-side checks on staging offsets, tile / split indices and output addresses; nor does a
+forward + backward of each per-pixel loss on the scalar path (3x25x41: two tiles, one pixel in the
+second) and on the 16-byte path (3x32x32)."""
 import os
 import subprocess
 import sys
@@ -37,6 +39,23 @@ for dtype, base, size, dual in (("bf16", 16, 72, False), ("fp32", 16, 40, False)
     st = _lib.debug_status()
     print(dtype, base, size, dual, "debug status", st)
     assert st == (0, 0), (dtype, base, size, dual, st)
+# the per-pixel losses (csrc/pixelloss.h's visits): two tiles with one pixel in the second on the scalar path, then
+# the 16-byte path
+from eunet import ops
+from eunet.losses import bce_dice_loss, boundary_loss
+for h, w in ((25, 41), (32, 32)):
+    torch.manual_seed(1)
+    t = torch.randint(0, 3, (3, h, w), device="cuda")
+    pw = torch.rand(3, h, w, device="cuda")
+    dist = ops.signed_distance_map(t, 3)
+    for name, fn in (("combined", lambda x: combined_loss(x, t)),
+                     ("bce_dice", lambda x: bce_dice_loss(x, t, pixel_weight=pw)),
+                     ("boundary", lambda x: boundary_loss(x, dist))):
+        x = torch.randn(3, 3, h, w, device="cuda", requires_grad=True)
+        fn(x).backward()
+        st = _lib.debug_status()
+        print(name, h, w, "debug status", st)
+        assert st == (0, 0), (name, h, w, st)
 print("DEBUG_OK")
 '''
 

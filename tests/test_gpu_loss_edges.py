@@ -173,6 +173,23 @@ def test_batch_of_64_and_65():
         combined_loss(x.to(DEV), t.to(DEV), params=REFERENCE.params(), track_targets=False)
 
 
+def test_entry_points_share_the_shape_rule():
+    """The one shape rule of the loss entry points (include/eunet.h, "per-pixel losses") holds for eunet_loss_fwd
+    and eunet_loss_bwd too: an empty plane and a backward over 65 samples are refused before any launch."""
+    from eunet import ops
+    from eunet._lib import EunetError
+    x, t, _ = _inputs(65, 3, 5, 7, seed=11)
+    x, t = x.to(DEV), t.to(DEV)
+    sums = torch.zeros(ops.loss_sums_len(65, 3), device=DEV)
+    loss, parts = torch.zeros((), device=DEV), torch.zeros(65, 3, device=DEV)
+    ws = torch.zeros(ops.loss_workspace_bytes(65, 3, 5, 7), dtype=torch.uint8, device=DEV)
+    # "bad args" is the shape rule's message: the refusal comes from the argument check, not from a failed launch
+    with pytest.raises(EunetError, match="loss_fwd: bad args"):
+        ops.loss_fwd(x[:3, :, :0], t[:3, :0], None, sums, loss, parts, ws)  # h = 0
+    with pytest.raises(EunetError, match="loss_bwd: bad args"):
+        ops.loss_bwd(x, t, None, sums, torch.ones(1, device=DEV), torch.empty_like(x))
+
+
 PARAM_SETS = {
     "reference": REFERENCE,
     "gamma0": Spec(gamma=0.0),

@@ -215,6 +215,24 @@ def test_weight_of_ones_is_the_unweighted_call_bit_for_bit(H, W, K, kind):
         assert torch.equal(a, b)
 
 
+def test_function_apply_as_called_before_the_weight_argument():
+    """BCEDiceFunction.apply(logits, target, params, track_targets), the four-argument call from before pixel_weight
+    became its optional fifth, is bce_dice_loss(logits, target): value, parts and gradient bit for bit (3x25x41,
+    K = 2)."""
+    from eunet.losses import BCEDiceFunction, bce_dice_loss
+    x, t, _ = _inputs(3, 2, 25, 41, seed=77, kind="bce")
+    outs = []
+    for call in (lambda xd, td: BCEDiceFunction.apply(xd, td, None, False),
+                 lambda xd, td: bce_dice_loss(xd, td, return_parts=True, track_targets=False)):
+        xd = x.to(DEV).requires_grad_(True)
+        loss, parts = call(xd, t.to(DEV))
+        loss.backward()
+        outs.append((loss.detach(), parts, xd.grad))
+    torch.cuda.synchronize()
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+
+
 def test_library_refusals():
     """focal_norm = 1 with a weight and a null weight are EUNET_ERR_INVALID in the library itself."""
     from eunet import _lib, ops
