@@ -53,6 +53,8 @@ EDT_NONE = 2 ** 31 - 1
 EDT_MAX_VALUES, EDT_MAX_SIDE = 8, 8192
 BOUNDARY_MAX_CAP, BOUNDARY_MAX_RADII = 64, 8
 BOUNDARY_SOFTMAX, BOUNDARY_SIGMOID = 0, 1  # EUNET_BOUNDARY_*
+LOVASZ_SOFTMAX, LOVASZ_HINGE = 0, 1  # EUNET_LOVASZ_* (activation)
+LOVASZ_PRESENT, LOVASZ_ALL, LOVASZ_LISTED = 0, 1, 2  # EUNET_LOVASZ_* (classes_mode)
 PAIRS_MAX_ID = 2 ** 24 - 1  # EUNET_PAIRS_MAX_ID
 CELL_GEOM_COLS = 14  # EUNET_CELL_GEOM_COLS
 CELL_HULL_COLS = 11  # EUNET_CELL_HULL_COLS
@@ -163,6 +165,12 @@ SIGNATURES = {
     "eunet_boundary_loss_workspace_bytes": [c_int, c_int, c_int, POINTER(c_size_t)],
     "eunet_boundary_loss_fwd": [_f, _f, c_int, c_int, c_int, c_int, c_int, POINTER(c_float * 3), _f, _f, _f, c_void_p],
     "eunet_boundary_loss_bwd": [_f, _f, c_int, c_int, c_int, c_int, c_int, POINTER(c_float * 3), _f, _f, c_void_p],
+    "eunet_lovasz_workspace_bytes": [c_int, c_int, POINTER(c_size_t)],
+    "eunet_lovasz_errors": [_f, _f, c_int, c_int, c_int, c_int, c_int, c_int, _f, _f, c_void_p],
+    "eunet_lovasz_sort": [_f, _f, c_int, c_int, _f, _f, _f, _f, c_void_p],
+    "eunet_lovasz_fwd": [_f, _f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, _f, _f, _f, _f, _f,
+                         _f, c_void_p],
+    "eunet_lovasz_bwd": [_f, _f, c_int, c_int, c_int, c_int, c_int, c_int, _f, _f, _f, _f, c_void_p],
     "eunet_tile_gather": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, c_void_p],
     "eunet_tile_blend": [_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _f, _f, c_int,
                          c_int, c_int, _f, c_void_p],

@@ -23,6 +23,10 @@ same counter and check_targets().
 boundary_loss / BoundaryLoss (csrc/sdf.hip) are the contour term: the softmax or sigmoid probability integrated
 against a signed distance map of the target (ops.signed_distance_map), after Kervadec et al. (MIDL 2019).  It sees
 no target, only the map, and is meant to be added to a region loss from the caller's own loop.
+
+lovasz_loss / LovaszLoss (csrc/lovasz.hip) are the IoU surrogate of Berman et al. (CVPR 2018): the errors of a class
+sorted on the device (a stable segmented radix sort) and weighted by the gradient of the Jaccard extension.  Like
+the boundary loss it is called from the caller's own loop; it reports refused targets through check_targets().
 """
 from __future__ import annotations
 
@@ -460,6 +464,102 @@ class BoundaryLoss(nn.Module):
         return self.weight * boundary_loss(logits, dist, activation=self.activation, class_weight=self.class_weight)
 
 
+# ---- Lovasz-Softmax and Lovasz hinge (csrc/lovasz.hip; Berman et al., CVPR 2018; include/eunet.h holds the definition)
+def _lovasz_classes(classes, activation: str, k: int, what: str):
+    """classes -> (classes_mode, class_mask) of eunet_lovasz_fwd.  None: "present" for softmax and "all" for hinge
+    (Berman's two defaults)."""
+    if classes is None:
+        classes = "present" if activation == "softmax" else "all"
+    if isinstance(classes, str):
+        if classes not in ("present", "all"):
+            raise ValueError(f"{what}: classes must be 'present', 'all' or a sequence of class indices, not {classes!r}")
+        return (_lib.LOVASZ_PRESENT if classes == "present" else _lib.LOVASZ_ALL), 0
+    try:
+        idx = [int(c) for c in classes]
+    except TypeError:
+        raise ValueError(f"{what}: classes must be 'present', 'all' or a sequence of class indices, not {classes!r}")
+    if not idx or any(not 0 <= c < k for c in idx):
+        raise ValueError(f"{what}: classes {list(classes)} must name at least one class of 0..{k - 1} and none beyond")
+    mask = 0
+    for c in idx:
+        mask |= 1 << c
+    return _lib.LOVASZ_LISTED, mask
+
+
+class LovaszFunction(torch.autograd.Function):
+    """eunet_lovasz_fwd / _bwd: apply(logits, target, activation, per_image, classes_mode, class_mask, ignore_index,
+    track_targets) -> (loss, parts).  Saves logits, target, the forward's weights (the Lovasz gradient g at every
+    element) and the per-segment factor table; parts takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, target, activation, per_image, classes_mode, class_mask, ignore_index, track_targets):
+        n, k, h, w = logits.shape
+        dev = logits.device
+        s, l = ops.lovasz_segments(n, k, h, w, per_image)
+        weights = torch.empty_like(logits)
+        factor = torch.empty(s, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts = torch.empty(s, dtype=torch.float32, device=dev)
+        bad = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = torch.empty(ops.lovasz_workspace_bytes(s, l), dtype=torch.uint8, device=dev)
+        ops.lovasz_fwd(logits, target, activation, per_image, classes_mode, class_mask, ignore_index, weights, factor,
+                       loss, parts, None, bad, ws)
+        if track_targets:
+            _record_bad(bad)
+        ctx.save_for_backward(logits, target, weights, factor)
+        ctx.conf = (activation, per_image)
+        ctx.mark_non_differentiable(parts)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, gloss, gparts):
+        logits, target, weights, factor = ctx.saved_tensors
+        activation, per_image = ctx.conf
+        glog = torch.empty_like(logits)
+        ops.lovasz_bwd(logits, target, activation, per_image, weights, factor, gloss.contiguous().float().reshape(1),
+                       glog)
+        return glog, None, None, None, None, None, None, None
+
+
+def lovasz_loss(logits: torch.Tensor, target: torch.Tensor, activation: str = "softmax", classes=None,
+                per_image: bool = False, ignore_index: Optional[int] = None, return_parts: bool = False,
+                validate: bool = False, track_targets: bool = True):
+    """The Lovasz-Softmax (activation="softmax", K = 2..3) or Lovasz hinge ("hinge", K = 1..3, one binary problem per
+    logit) loss: logits float32 [N,K,H,W] (N <= 64), target int64 [N,H,W], both contiguous on one GPU.  Per segment
+    (a class over the batch, or with per_image a class of one sample) the errors are sorted descending and weighted
+    by the gradient of the Jaccard extension; the loss is the mean over the selected segments (per_image: the mean
+    over samples of each sample's mean).  classes: "present" (segments with foreground), "all" (segments with a
+    valid pixel) or a sequence of class indices; None = "present" for softmax, "all" for hinge.  Pixels at
+    ignore_index count nowhere; other invalid targets count nowhere either and are reported by check_targets() (at
+    once with validate=True).  parts: float32 [S] segment losses, NaN where a segment was not selected."""
+    ign = ops._check_lovasz_args(logits, target, activation, ignore_index, "lovasz_loss",
+                                 more=lambda: _lovasz_classes(classes, activation, logits.shape[1], "lovasz_loss"))
+    mode, mask = _lovasz_classes(classes, activation, logits.shape[1], "lovasz_loss")
+    loss, parts = LovaszFunction.apply(logits, target, ops.LOVASZ_ACTIVATIONS[activation], bool(per_image), mode, mask,
+                                       ign, track_targets)
+    if validate:
+        check_targets()
+    return (loss, parts) if return_parts else loss
+
+
+class LovaszLoss(nn.Module):
+    """weight * lovasz_loss(logits, target) with its configuration held as attributes: set them at any time, the next
+    call reads them."""
+
+    def __init__(self, activation: str = "softmax", classes=None, per_image: bool = False,
+                 ignore_index: Optional[int] = None, weight: float = 1.0):
+        super().__init__()
+        self.activation = activation
+        self.classes = classes
+        self.per_image = per_image
+        self.ignore_index = ignore_index
+        self.weight = weight
+
+    def forward(self, logits, target):
+        return self.weight * lovasz_loss(logits, target, activation=self.activation, classes=self.classes,
+                                         per_image=self.per_image, ignore_index=self.ignore_index)
+
+
 def _as_pixels(inputs: torch.Tensor, targets: torch.Tensor):
     """[N,K,*] logits / [N,*] targets -> [1,K,1,P] / [1,1,P] (pixel-mean losses only)."""
     if inputs.dim() < 2:
@@ -532,4 +632,5 @@ def tversky_loss(pred, target, num_classes: int = 3, alpha: float = 0.7):
 
 __all__ = ["combined_loss", "consistency_loss", "check_targets", "make_params", "reference_params", "FocalLoss",
            "CrossEntropyLoss", "dice_loss", "tversky_loss", "make_bce_dice_params", "BCEDiceFunction", "bce_dice_loss",
-           "BCEDiceLoss", "BoundaryLossFunction", "boundary_loss", "BoundaryLoss"]
+           "BCEDiceLoss", "BoundaryLossFunction", "boundary_loss", "BoundaryLoss", "LovaszFunction", "lovasz_loss",
+           "LovaszLoss"]

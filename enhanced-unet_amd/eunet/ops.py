@@ -1226,6 +1226,135 @@ def boundary_loss_bwd(logits, dist, activation, cw0, cw1, cw2, gloss, glogits):
              _ptr(glogits), _stream())
 
 
+# ---- Lovasz losses (lovasz.hip; include/eunet.h, "Lovasz losses") -----------------------------
+LOVASZ_ACTIVATIONS = {"softmax": _lib.LOVASZ_SOFTMAX, "hinge": _lib.LOVASZ_HINGE}  # EUNET_LOVASZ_*
+_NO_IGNORE = -(2 ** 31)  # EUNET_NO_IGNORE
+
+
+def lovasz_workspace_bytes(s, l):
+    """The workspace of a call over s segments of l elements (a function of the shape alone)."""
+    b = c_size_t()
+    call("eunet_lovasz_workspace_bytes", s, l, ctypes.byref(b))
+    return b.value
+
+
+def lovasz_segments(n, k, h, w, per_image):
+    """(S, L): K segments of N H W elements, or per image N K segments of H W."""
+    return (n * k, h * w) if per_image else (k, n * h * w)
+
+
+def _check_lovasz_args(logits, target, activation, ignore_index, what: str, more=None):
+    """The rules of the Lovasz ops that need no launch, raised as ValueError; returns ignore_index as the int32 of the
+    C ABI.  more(): the caller's own value rules, checked after the shapes and before the device."""
+    if activation not in LOVASZ_ACTIVATIONS:
+        raise ValueError(f"{what}: activation must be 'softmax' or 'hinge', not {activation!r}")
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
+        raise ValueError(f"{what}: expected [N, K, H, W] logits, got "
+                         f"{tuple(logits.shape) if isinstance(logits, torch.Tensor) else type(logits).__name__}")
+    if not isinstance(target, torch.Tensor):
+        raise ValueError(f"{what}: target must be a tensor, got {type(target).__name__}")
+    if logits.dtype != torch.float32:
+        raise ValueError(f"{what}: logits must be float32, got {logits.dtype}")
+    if target.dtype != torch.int64:
+        raise ValueError(f"{what}: target must be int64, got {target.dtype}")
+    n, k, h, w = logits.shape
+    if tuple(target.shape) != (n, h, w):
+        raise ValueError(f"{what}: target {tuple(target.shape)} does not match logits {tuple(logits.shape)}")
+    if not (1 <= n <= 64 and 1 <= k <= 3 and h > 0 and w > 0 and h * w < 2 ** 31 - 1024 and n * h * w < 2 ** 31):
+        raise ValueError(f"{what}: logits {tuple(logits.shape)} are outside the shape rule (N 1..64, K 1..3, H > 0, "
+                         f"W > 0, H*W < 2^31 - 1024, N*H*W < 2^31)")
+    if activation == "softmax" and k == 1:
+        raise ValueError(f"{what}: a softmax over K = 1 is constant; use activation='hinge'")
+    ign = _NO_IGNORE if ignore_index is None else int(ignore_index)
+    if not -2 ** 31 <= ign < 2 ** 31:
+        raise ValueError(f"{what}: ignore_index {ignore_index} is not an int32")
+    if more is not None:
+        more()
+    if not logits.is_contiguous() or not target.is_contiguous():
+        raise ValueError(f"{what}: logits and target must be contiguous")
+    if not logits.is_cuda or target.device != logits.device:
+        raise ValueError(f"{what}: logits and target must live on one GPU, got {logits.device} and {target.device}")
+    return ign
+
+
+@_dispatched("T T i i T! T!")
+def lovasz_errors_op(logits, target, activation, ignore_index, errors, flags):
+    """torch.ops.eunet.lovasz_errors_op: the errors and flags of every (pixel, class) into errors and flags."""
+    n, k, h, w = logits.shape
+    with kprof.timed("lovasz_errors", 0.0, 9.0 * logits.numel() + 8.0 * target.numel()):
+        call("eunet_lovasz_errors", _ptr(logits), _ptr(target), n, k, h, w, activation, ignore_index, _ptr(errors),
+             _ptr(flags), _stream())
+
+
+def lovasz_errors(logits, target, activation, ignore_index=None):
+    """logits float32 [N,K,H,W], target int64 [N,H,W] -> (errors float32 [N,K,H,W], flags uint8 [N,K,H,W]): per
+    element the error of the Lovasz loss (softmax: |fg - p_c|; hinge: 1 - z_c (2 fg - 1)) and its flag, 0 background,
+    1 foreground, 2 ignored or out of range (error 0)."""
+    ign = _check_lovasz_args(logits, target, activation, ignore_index, "lovasz_errors")
+    errors = torch.empty_like(logits)
+    flags = torch.empty(logits.shape, dtype=torch.uint8, device=logits.device)
+    lovasz_errors_op(logits, target, LOVASZ_ACTIVATIONS[activation], ign, errors, flags)
+    return errors, flags
+
+
+@_dispatched("T T T! T! T! T!")
+def lovasz_sort_op(errors, flags, order, grad, counts, ws):
+    s, l = errors.shape
+    with kprof.timed("lovasz_sort", 0.0, 160.0 * errors.numel()):
+        call("eunet_lovasz_sort", _ptr(errors), _ptr(flags), s, l, _ptr(order), _ptr(grad), _ptr(counts), _ptr(ws),
+             _stream())
+
+
+def lovasz_sort(errors, flags):
+    """errors float32 [S,L], flags uint8 [S,L] (0 background, 1 foreground, >= 2 ignored) -> (order int32 [S,L], grad
+    float32 [S,L], counts int64 [S,2]): per segment the stable descending order of the valid errors (ignored
+    elements last, in index order), the Lovasz gradient g at every element's own index (0 where ignored), and
+    (G, V), the foreground and valid counts."""
+    name = "lovasz_sort"
+    for what, t, dt in (("errors", errors, torch.float32), ("flags", flags, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{name}: {what} must be a [S, L] tensor")
+        if t.dtype != dt:
+            raise ValueError(f"{name}: {what} must be {dt}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous")
+    if errors.shape != flags.shape:
+        raise ValueError(f"{name}: errors {tuple(errors.shape)} and flags {tuple(flags.shape)} differ in shape")
+    s, l = errors.shape
+    if not (1 <= s <= 65535 and 1 <= l < 2 ** 31):
+        raise ValueError(f"{name}: S must be 1..65535 and L 1..2^31-1, got {s} x {l}")
+    if not errors.is_cuda or flags.device != errors.device:
+        raise ValueError(f"{name}: errors and flags must live on one GPU, got {errors.device} and {flags.device}")
+    dev = errors.device
+    order = torch.empty((s, l), dtype=torch.int32, device=dev)
+    grad = torch.empty((s, l), dtype=torch.float32, device=dev)
+    counts = torch.empty((s, 2), dtype=torch.int64, device=dev)
+    ws = torch.empty(lovasz_workspace_bytes(s, l), dtype=torch.uint8, device=dev)
+    lovasz_sort_op(errors, flags, order, grad, counts, ws)
+    return order, grad, counts
+
+
+@_dispatched("T T i b i i i T! T! T! T!? T!? T!? T!")
+def lovasz_fwd(logits, target, activation, per_image, classes_mode, class_mask, ignore_index, weights, factor, loss,
+               parts, counts, bad, ws):
+    """torch.ops.eunet.lovasz_fwd: weights [N,K,H,W] = g at every element, factor [S] = the segments' shares of the
+    mean, loss, parts [S], counts [S,2] = (G, V), bad [1] = the out-of-range targets."""
+    n, k, h, w = logits.shape
+    with kprof.timed("lovasz_fwd", 0.0, 170.0 * logits.numel()):
+        call("eunet_lovasz_fwd", _ptr(logits), _ptr(target), n, k, h, w, activation, int(per_image), classes_mode,
+             class_mask, ignore_index, _ptr(weights), _ptr(factor), _ptr(loss), _ptr(parts), _ptr(counts), _ptr(bad),
+             _ptr(ws), _stream())
+
+
+@_dispatched("T T i b T T T T!")
+def lovasz_bwd(logits, target, activation, per_image, weights, factor, gloss, glogits):
+    """torch.ops.eunet.lovasz_bwd: glogits = gloss * d loss / d logits from the forward's weights and factor."""
+    n, k, h, w = logits.shape
+    with kprof.timed("lovasz_bwd", 0.0, 12.0 * logits.numel() + 8.0 * target.numel()):
+        call("eunet_lovasz_bwd", _ptr(logits), _ptr(target), n, k, h, w, activation, int(per_image), _ptr(weights),
+             _ptr(factor), _ptr(gloss), _ptr(glogits), _stream())
+
+
 # ---- overlap-tile inference (tiling.hip; the geometry is eunet.tiling.TilePlan) ----------
 TILE_ACTIVATIONS = {"none": 0, "softmax": 1, "sigmoid": 2}  # EUNET_TILE_ACT_*
 

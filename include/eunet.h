@@ -241,8 +241,8 @@ int eunet_head_bwd(const float* z, int n, int h, int w, int k, const float* w1, 
                    int dtype, void* ws, void* stream);
 
 /* ---- per-pixel losses: the shape rule --------------------------------------
- * Every forward and backward entry point of the three per-pixel losses below (eunet_loss_*, eunet_bce_dice_*,
- * eunet_boundary_loss_*, the _w variants included) takes logits [N,K,H,W] fp32 NCHW with
+ * Every forward and backward entry point of the per-pixel losses below (eunet_loss_*, eunet_bce_dice_*,
+ * eunet_boundary_loss_*, eunet_lovasz_errors / _fwd / _bwd, the _w variants included) takes logits [N,K,H,W] fp32 NCHW with
  *   N in 1..64, K in 1..3, H > 0, W > 0 and H*W < 2^31 - 1024,
  * and returns EUNET_ERR_INVALID for anything else, before any launch (csrc/pixelloss.h, pl_shape_ok).  N <= 64
  * is the finalize block's per-sample storage; the last bound keeps a plane index plus one tile of 1024 pixels in
@@ -466,7 +466,8 @@ int eunet_bn_bwd_apply(const eunet_act* g, const eunet_act* y, const float* mean
  * eunet_debug_status: synchronises the device; *count = failed checks since the last reset,
  * *unit_line = unit * 100000 + source line of the first (units: 1 capi, 2 conv3x3, 3 bn_pool_up,
  * 4 head, 5 instances, 6 baselines, 7 upconv, 8 bce_dice, 9 weightmap, 10 tiling, 11 warp,
- * 12 boundary, 13 watershed, 14 pairs, 15 sdf; 0 = none).  eunet_debug_selftest launches one deliberately failing check (capi unit). */
+ * 12 boundary, 13 watershed, 14 pairs, 15 sdf, 16 cellprops, 17 hull, 18 loss, 19 lovasz; 0 = none).
+ * eunet_debug_selftest launches one deliberately failing check (capi unit). */
 int eunet_debug_enabled(void);
 int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset);
 int eunet_debug_selftest(void* stream);
@@ -864,6 +865,73 @@ int eunet_boundary_loss_fwd(const float* logits, const float* dist, int n, int k
                             const float* class_weight, float* loss, float* parts, void* ws, void* stream);
 int eunet_boundary_loss_bwd(const float* logits, const float* dist, int n, int k, int h, int w, int activation,
                             const float* class_weight, const float* gloss, float* glogits, void* stream);
+
+/* ---- Lovasz losses (lovasz.hip) -----------------------------------------------
+ * No reference line to cite: every loss of the reference is a sum over pixels, and its metrics are IoU.  The
+ * Lovasz-Softmax and Lovasz hinge losses of Berman, Triki and Blaschko, "The Lovasz-Softmax loss: a tractable
+ * surrogate for the optimization of the intersection-over-union measure in neural networks" (CVPR 2018), are the
+ * convex extension of the Jaccard set loss; this comment is their definition here.
+ *
+ * Elements and segments.  logits fp32 [N][K][H][W] (the shape rule of the per-pixel losses, and N H W < 2^31),
+ * target int64 [N][H][W].  per_image = 0: S = K segments (one per class) of L = N H W elements, an element's index
+ * in its segment being n H W + y W + x.  per_image = 1: S = N K segments, segment n K + c, of L = H W elements with
+ * the index y W + x.
+ * Errors and flags of element (n, c, x):
+ *   EUNET_LOVASZ_SOFTMAX (K = 2, 3): p = softmax over c (max-subtracted), fg = [target == c], e = |fg - p_c|
+ *   EUNET_LOVASZ_HINGE   (K = 1..3, one binary problem per logit z_c): fg = [target == c], for K = 1
+ *       fg = [target >= 1] (EUNET_BCE_TARGET_FOREGROUND's rule); e = 1 - z_c (2 fg - 1).  The loss uses max(e, 0),
+ *       the order e itself (Berman's lovasz_hinge_flat).
+ *   flag = 0 background, 1 foreground, 2 ignored: target == ignore_index (EUNET_NO_IGNORE = none), or a target
+ *       outside 0 .. K-1 (for the hinge with K = 1: below 0), which is also counted (`bad`, reported the way
+ *       eunet_bce_dice_fwd's last sum is).  A flag-2 element takes part in nothing; eunet_lovasz_errors writes 0
+ *       for its error.
+ * Order.  In a segment the valid elements are ordered by error descending, equal errors by index ascending (the
+ * sort is stable), the ignored ones follow in index order.  -0 counts as +0; a NaN sorts ahead of +inf (as
+ * torch.sort(descending=True) places it; the loss is then NaN, and nothing is read or stored out of range).
+ * Gradient of the extension, from integers.  G = the segment's foreground count, V = its valid count, F_r = the
+ * foreground count among the first r sorted elements (r = 1..V), I_r = G - F_r, U_r = G + r - F_r:
+ *   g_r = 1 / U_r                        the element of rank r is foreground
+ *   g_r = I_r / ((U_r - 1) U_r)          it is background
+ *   g_1 = 1, g_r = 0 otherwise           G = 0
+ * (J_r - J_{r-1} of the paper in closed form), evaluated as double(I) / (double(U - 1) * double(U)) or
+ * 1.0 / double(U) and rounded once to fp32: correctly rounded operations on integers, the same bits anywhere.
+ * Loss.  l_s = sum_r eb_(r) g_r, eb = e (softmax) or max(e, 0) (hinge), in fp64 in a fixed order (per-block
+ * partials, one finalize block): two runs are bit-identical.  A segment is selected by classes_mode:
+ * EUNET_LOVASZ_PRESENT G > 0, EUNET_LOVASZ_ALL V > 0, EUNET_LOVASZ_LISTED V > 0 and bit c of class_mask set.
+ * per_image = 0: loss = the mean of l_s over the selected segments; per_image = 1: the mean over the N samples of
+ * the mean over each sample's selected segments.  An empty mean is 0.  The selection is made on the device.
+ *
+ * eunet_lovasz_errors: errors fp32 and flags uint8, both [N][K][H][W].
+ * eunet_lovasz_sort: errors fp32 and flags uint8 [S][L] (S <= 65535, L < 2^31; a flag >= 2 is ignored) -> order
+ *   int32 [S][L] (the permutation: order[s][r] = the index of the element of rank r+1, ignored ones last), grad
+ *   fp32 [S][L] (g at the element's own index, 0 where ignored), counts int64 [S][2] = (G, V).
+ * eunet_lovasz_fwd: weights fp32 [N][K][H][W] = g at every element's own position (0 where ignored), factor fp32
+ *   [S] = the segment's share of the mean (1 / #selected, per_image: 1 / (N #selected of the sample); 0 for a
+ *   segment that is not selected), loss 1 fp32, parts (nullable) fp32 [S] = l_s, NaN where not selected, counts
+ *   (nullable) int64 [S][2], bad (nullable) 1 fp32 = the out-of-range targets.  The scaling of weights is left to
+ *   the backward: it multiplies by factor[segment] as it reads.
+ * eunet_lovasz_bwd: glogits = (*gloss) d loss / d z with w_c = weights factor[segment], one pass (16 bytes per lane
+ *   when H W % 4 == 0 and the pointers are 16-byte aligned):
+ *   softmax: sum_c w_c s_c p_c ([c == j] - p_j), s_c = sign(p_c - fg_c), sign(0) = 0 (torch.abs's derivative)
+ *   hinge:   -w_c (2 fg_c - 1) [e_c > 0]
+ * ws: eunet_lovasz_workspace_bytes(S, L) for S segments of L elements, a function of the shape alone: keys and
+ * payloads, both double-buffered (16 bytes per element), the sort's block x digit table, the scan's block counts, the
+ * per-block count rows and
+ * the fp64 partials; 256-byte aligned.  All K classes are sorted at once.  Every call issues launches on the given
+ * stream only: no host read-back, no allocation. */
+enum { EUNET_LOVASZ_SOFTMAX = 0, EUNET_LOVASZ_HINGE = 1 };
+enum { EUNET_LOVASZ_PRESENT = 0, EUNET_LOVASZ_ALL = 1, EUNET_LOVASZ_LISTED = 2 };
+int eunet_lovasz_workspace_bytes(int s, int l, size_t* bytes);
+int eunet_lovasz_errors(const float* logits, const int64_t* target, int n, int k, int h, int w, int activation,
+                        int ignore_index, float* errors, uint8_t* flags, void* stream);
+int eunet_lovasz_sort(const float* errors, const uint8_t* flags, int s, int l, int32_t* order, float* grad,
+                      int64_t* counts, void* ws, void* stream);
+int eunet_lovasz_fwd(const float* logits, const int64_t* target, int n, int k, int h, int w, int activation,
+                     int per_image, int classes_mode, int class_mask, int ignore_index, float* weights,
+                     float* factor, float* loss, float* parts, int64_t* counts, float* bad, void* ws, void* stream);
+int eunet_lovasz_bwd(const float* logits, const int64_t* target, int n, int k, int h, int w, int activation,
+                     int per_image, const float* weights, const float* factor, const float* gloss, float* glogits,
+                     void* stream);
 
 /* ---- overlap-tile inference (tiling.hip) -------------------------------------
  * Prediction on an image larger than one forward pass (no reference line: the reference's only answer to a
