@@ -45,6 +45,7 @@ int debug_read_cellprops(unsigned*, unsigned*, bool);
 int debug_read_hull(unsigned*, unsigned*, bool);
 int debug_read_loss(unsigned*, unsigned*, bool);
 int debug_read_lovasz(unsigned*, unsigned*, bool);
+int debug_read_neighbors(unsigned*, unsigned*, bool);
 #endif
 }  // namespace eunet
 
@@ -89,7 +90,7 @@ int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset) {
     eunet::set_error("debug_status: device synchronisation failed");
     return EUNET_ERR_HIP;
   }
-  constexpr int UNITS = 19;  // a new unit is appended: the unit numbers of eunet_debug_status stay
+  constexpr int UNITS = 20;  // a new unit is appended: the unit numbers of eunet_debug_status stay
   int (*readers[UNITS])(unsigned*, unsigned*, bool) = {eunet::debug_read_capi, eunet::debug_read_conv3x3,
                                                    eunet::debug_read_bnpool, eunet::debug_read_head,
                                                    eunet::debug_read_instances, eunet::debug_read_baselines,
@@ -99,7 +100,7 @@ int eunet_debug_status(unsigned* unit_line, unsigned* count, int reset) {
                                                    eunet::debug_read_watershed, eunet::debug_read_pairs,
                                                    eunet::debug_read_sdf, eunet::debug_read_cellprops,
                                                    eunet::debug_read_hull, eunet::debug_read_loss,
-                                                   eunet::debug_read_lovasz};
+                                                   eunet::debug_read_lovasz, eunet::debug_read_neighbors};
   for (int u = 0; u < UNITS; ++u) {
     unsigned line = 0, cnt = 0;
     const int rc = readers[u](&line, &cnt, reset != 0);

@@ -1,5 +1,5 @@
 // Shared helpers of the label-map units (instances, boundary, curves, watershed, pairs, sdf, cellprops, hull,
-// evalpath): launch sizing, cleared buffers, the plane-stack shape rule, integer wave reductions, the flag scan that
+// neighbors, evalpath): launch sizing, cleared buffers, the plane-stack shape rule, integer wave reductions, the flag scan that
 // numbers things in raster order, and the open-addressing hash table.  All of it is integer and exact.
 //
 // Debug build: table_update asserts, and EUNET_DASSERT writes to the including unit's g_eunet_dbg, which

@@ -191,6 +191,9 @@ SIGNATURES = {
     "eunet_labels_from_stack": [_f, c_int, c_int, c_int, _f, _f, _f, _f, c_void_p],
     "eunet_cell_stats": [_f, c_int, c_int, c_int, c_int, c_int, _f, c_int, _f, _f, _f, c_void_p],
     "eunet_cell_hulls": [_f, c_int, c_int, c_int, c_int, c_int, _f, _f, _f, _f, _f, _f, c_void_p],
+    "eunet_nearest_site": [_f, c_int, c_int, c_int, c_int, _f, _f, c_void_p],
+    "eunet_expand_label_map": [_f, c_int, c_int, c_int, c_int, ctypes.c_longlong, _f, _f, c_void_p],
+    "eunet_label_contacts": [_f, c_int, c_int, c_int, c_int, c_int, _f, _f, ctypes.c_longlong, _f, _f, c_void_p],
     "eunet_outer_perimeter": [_f, c_int, c_int, c_int, _f, _f, c_void_p],
     "eunet_mask_eq": [_f, c_int, c_int64, c_int64, _f, _f, c_void_p],
     "eunet_mask_and": [_f, _f, c_int64, _f, _f, c_void_p],

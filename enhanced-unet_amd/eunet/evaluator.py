@@ -79,6 +79,11 @@ metrics.cell_measurements turns into area, centroid, axes, orientation, perimete
 intensity of every cell; evaluate_measurements compares the areas and centroids of the predicted cells with those of
 the ground-truth cells they match at IoU > 1/2.
 
+Cells in relation to each other (measure_neighbors; no reference counterpart): the two class planes are pooled into
+one id map, grown by ops.expand_label_map (neighbors.hip) by a distance or to the Voronoi partition, and
+ops.label_contacts' table of the grown map gives metrics.neighbor_measurements the neighbour counts, shared borders,
+territories and closest-cell distances of every cell, and the contact graph.
+
 Overlap-tile inference (no reference counterpart: the reference resizes every image down to max_size):
 Evaluator(..., tile=T) sends an image whose padded size exceeds T in either axis through the network tile by
 tile (eunet.tiling.plan; ops.tile_gather, forward_lowres on tile_batch tiles at a time, one ops.tile_blend
@@ -103,7 +108,7 @@ from .metrics import (CLASS_NAMES, INSTANCE_CLASSES, PANOPTIC_IOU_PERCENT, SIZE_
                       calculate_viability_metrics, coco_image_matches, coco_map_from_matches, curve_edges,
                       curve_metrics_from_hist, instance_stats_from_pairs, panoptic_keys, panoptic_metrics_from_stats,
                       size_strata_from_pairs, AGREEMENT_KEYS, agreement_summary, cell_measurements,
-                      hull_measurements, measurement_agreement)
+                      hull_measurements, measurement_agreement, neighbor_graph, neighbor_measurements)
 
 TTA_SCALES = (0.75, 1.25)
 
@@ -639,6 +644,32 @@ class Evaluator:
         n_live, n_dead = int(counts[0]), int(counts[1])
         out.update(n_live=n_live, n_dead=n_dead, viability=n_live / (n_live + n_dead) if n_live + n_dead else 0.0)
         return out
+
+    def measure_neighbors(self, image: torch.Tensor, distance=None, min_area: int = 3, pixel_size: float = 1.0,
+                          connectivity: int = 4) -> Dict:
+        """What the predicted cells of one image are to each other: semantic_to_instance_maps' [2, h, w] ids are pooled
+        into one plane (live ids 1..n_live, dead ids n_live + 1..n_live + n_dead: the class planes are disjoint by
+        construction), the plane is grown by `distance` pixels, or to the Voronoi partition of the image when distance
+        is None (ops.expand_label_map), and the grown map's contact table (ops.label_contacts) and the ops.cell_stats
+        tables of both maps go through metrics.neighbor_measurements -> {"live": m, "dead": m, "n_live", "n_dead",
+        "graph": metrics.neighbor_graph's CSR arrays over the pooled ids}, m = the measurement dict restricted to the
+        class plus "n_neighbors_same_class".  first_closest_id / second_closest_id are pooled ids."""
+        self._label_map_models_only("measure_neighbors")
+        if connectivity not in (4, 8):
+            raise ValueError(f"measure_neighbors: connectivity must be 4 or 8, got {connectivity!r}")
+        ids, counts, _ = self.semantic_to_instance_maps(self._predict_mask_device(image), min_area)
+        n_live, n_dead = int(counts[0]), int(counts[1])
+        n = n_live + n_dead
+        pooled = (ids[0] + torch.where(ids[1] > 0, ids[1] + n_live, torch.zeros_like(ids[1]))).contiguous()
+        grown = ops.expand_label_map(pooled, distance)
+        contacts = ops.label_contacts(grown, connectivity)
+        m = neighbor_measurements(contacts, ops.cell_stats(pooled, n), ops.cell_stats(grown, n), 0, pixel_size)
+        indptr, indices, weights = neighbor_graph(contacts, 0, n)
+        owner = np.repeat(np.arange(n), np.diff(indptr))
+        same = np.bincount(owner[(owner < n_live) == (indices - 1 < n_live)], minlength=n)[:n].astype(np.float64)
+        m["n_neighbors_same_class"] = same
+        return {"live": {k: v[:n_live] for k, v in m.items()}, "dead": {k: v[n_live:] for k, v in m.items()},
+                "n_live": n_live, "n_dead": n_dead, "graph": (indptr, indices, weights)}
 
     def evaluate_measurements(self, dataloader, min_area: int = 3) -> Dict[str, float]:
         """How the measurements of the predicted cells agree with the ground truth's over the loader: per item the

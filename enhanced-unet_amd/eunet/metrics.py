@@ -1082,6 +1082,116 @@ def population_summary(measurements: Dict[str, np.ndarray], keys: Sequence[str] 
     return out
 
 
+# ---- cells in relation to each other (the tables of ops.label_contacts and ops.cell_stats, neighbors.hip) --------
+NEIGHBOR_KEYS = ("area", "n_neighbors", "shared_border", "touching_fraction", "territory_area",
+                 "first_closest_distance", "second_closest_distance", "first_closest_id", "second_closest_id",
+                 "angle_between_neighbors")
+
+
+def _contact_rows(contacts, plane: int, n: int, what: str) -> np.ndarray:
+    """The rows (a, b, count) of one plane of ops.label_contacts' table, checked: 1 <= a < b <= n, count >= 1."""
+    rows = np.asarray(contacts)
+    if rows.ndim != 2 or rows.shape[1] != 4 or rows.dtype != np.int64:
+        raise ValueError(f"{what}: contacts must be int64 [m, 4] rows (plane, a, b, n), got {rows.dtype} {rows.shape}")
+    rows = rows[rows[:, 0] == plane][:, 1:]
+    if len(rows) and not ((rows[:, 0] >= 1) & (rows[:, 0] < rows[:, 1]) & (rows[:, 1] <= n) & (rows[:, 2] >= 1)).all():
+        raise ValueError(f"{what}: a contact row of plane {plane} is not 1 <= a < b <= {n} with a count >= 1")
+    if len(np.unique(rows[:, :2], axis=0)) != len(rows):
+        raise ValueError(f"{what}: a pair of labels has two rows in plane {plane}")
+    return rows
+
+
+def neighbor_graph(contacts, plane: int, n: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The contact graph of the labels 1..n of one plane of ops.label_contacts' table -> the CSR arrays (indptr int64
+    [n + 1], indices int64, weights int64): the neighbours of label i are the labels indices[indptr[i - 1]:
+    indptr[i]] (ids, ascending), weights the contact counts of those pairs.  Symmetric: every row (a, b, c) of the
+    table gives b among a's neighbours and a among b's, both with weight c."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"neighbor_graph: n must be >= 0, got {n}")
+    rows = _contact_rows(contacts, plane, n, "neighbor_graph")
+    src = np.concatenate([rows[:, 0], rows[:, 1]])
+    dst = np.concatenate([rows[:, 1], rows[:, 0]])
+    wts = np.concatenate([rows[:, 2], rows[:, 2]])
+    order = np.lexsort((dst, src))
+    indptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(src - 1, minlength=n)[:n], out=indptr[1:])
+    return indptr, dst[order].astype(np.int64), wts[order].astype(np.int64)
+
+
+def neighbor_measurements(contacts, stats: Dict, stats_expanded: Dict, plane: int = 0, pixel_size: float = 1.0
+                          ) -> Dict[str, np.ndarray]:
+    """What the labels 1..n of one plane are to each other (CellProfiler's MeasureObjectNeighbors): contacts is
+    ops.label_contacts' table of the EXPANDED map (ops.expand_label_map), stats ops.cell_stats' result of the original
+    map and stats_expanded that of the expanded one, both for the same n -> {name: float64 [n]}, entry i - 1 for label
+    i.  numpy only, float64 from the integer tables.
+      area                     of the original label (what population_summary counts the present labels by)
+      n_neighbors              the labels it shares a contact row with
+      shared_border            the sum of its contact counts; at connectivity 4 the pixel sides it shares with others
+      touching_fraction        that sum over the crack perimeter q1 + q2 + q3 + 2 qd of the expanded label: at
+                               connectivity 4 both count pixel sides, so it lies in [0, 1]; 0 for a label with no pixel
+      territory_area           the area of the expanded label
+      first_closest_distance, second_closest_distance   between its centroid and the nearest and second nearest
+                               centroid of the other labels of the plane that have a pixel (the original map's
+                               centroids; the smaller id among equally near ones first); NaN where there are fewer
+                               than 2 or 3 such labels, and for a label with no pixel
+      first_closest_id, second_closest_id   the ids of those two labels (NaN likewise)
+      angle_between_neighbors  the angle at the label's centroid between those two, in degrees, 0..180
+    pixel_size s scales the lengths (shared_border, the distances) by s and the areas by s^2."""
+    what = "neighbor_measurements"
+    geom, geom_e = np.asarray(stats["geom"]), np.asarray(stats_expanded["geom"])
+    if geom.ndim != 3 or geom.shape[2] != 14 or geom.dtype != np.int64:
+        raise ValueError(f"{what}: geom must be int64 [p, n + 1, 14], got {geom.dtype} {geom.shape}")
+    if geom_e.shape != geom.shape or geom_e.dtype != np.int64:
+        raise ValueError(f"{what}: the expanded map's geom must be int64 {geom.shape}, got {geom_e.dtype} "
+                         f"{geom_e.shape}")
+    if not 0 <= plane < geom.shape[0]:
+        raise ValueError(f"{what}: plane {plane} of {geom.shape[0]}")
+    s = float(pixel_size)
+    if not (s > 0.0 and np.isfinite(s)):
+        raise ValueError(f"{what}: pixel_size must be positive and finite, got {pixel_size!r}")
+    g, e = geom[plane, 1:], geom_e[plane, 1:]
+    n = len(g)
+    indptr, indices, weights = neighbor_graph(contacts, plane, n)
+    degree = np.diff(indptr).astype(np.float64)
+    shared = np.zeros(n, np.float64)
+    np.add.at(shared, np.repeat(np.arange(n), np.diff(indptr)), weights.astype(np.float64))
+    crack = (e[:, 10] + e[:, 11] + e[:, 12] + 2 * e[:, 13]).astype(np.float64)
+    present = g[:, 0] > 0
+    cx = _int_ratios([int(v) for v in g[:, 1]], [int(v) for v in g[:, 0]])
+    cy = _int_ratios([int(v) for v in g[:, 2]], [int(v) for v in g[:, 0]])
+    ids = np.flatnonzero(present)  # label - 1 of the labels with a pixel, ascending
+    near = np.full((n, 2), np.nan)
+    near_id = np.full((n, 2), np.nan)
+    angle = np.full(n, np.nan)
+    for lo in range(0, len(ids), 1024):  # a block of rows of the centroid distance matrix at a time
+        rows = ids[lo:lo + 1024]
+        dx, dy = cx[ids][None, :] - cx[rows][:, None], cy[ids][None, :] - cy[rows][:, None]
+        d2 = dx * dx + dy * dy
+        d2[np.arange(len(rows)), lo + np.arange(len(rows))] = np.inf  # not its own neighbour
+        order = np.argsort(d2, axis=1, kind="stable")[:, :2]  # stable: the smaller id among equally near ones
+        for k in range(min(2, len(ids) - 1)):
+            j = order[:, k]
+            near[rows, k] = np.sqrt(d2[np.arange(len(rows)), j])
+            near_id[rows, k] = ids[j] + 1.0
+        if len(ids) >= 3:
+            r = np.arange(len(rows))
+            ax, ay, bx, by = dx[r, order[:, 0]], dy[r, order[:, 0]], dx[r, order[:, 1]], dy[r, order[:, 1]]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                cos = (ax * bx + ay * by) / np.sqrt((ax * ax + ay * ay) * (bx * bx + by * by))
+            angle[rows] = np.degrees(np.arccos(np.clip(cos, -1.0, 1.0)))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        touching = np.where(crack > 0.0, shared / np.where(crack > 0.0, crack, 1.0), 0.0)
+    out = {
+        "area": g[:, 0].astype(np.float64) * s * s, "n_neighbors": degree, "shared_border": shared * s,
+        "touching_fraction": touching, "territory_area": e[:, 0].astype(np.float64) * s * s,
+        "first_closest_distance": near[:, 0] * s, "second_closest_distance": near[:, 1] * s,
+        "first_closest_id": near_id[:, 0], "second_closest_id": near_id[:, 1], "angle_between_neighbors": angle,
+    }
+    assert tuple(out) == NEIGHBOR_KEYS and all(len(v) == n for v in out.values())
+    return out
+
+
 def measurement_agreement(pairs, geom_pred, geom_gt, plane: int) -> Dict:
     """How the measurements of one class plane's predicted cells agree with the ground truth's: pairs are the rows
     (plane, a, b, n) of ops.label_pairs(prediction ids, ground-truth ids), geom_pred / geom_gt the "geom" tables of

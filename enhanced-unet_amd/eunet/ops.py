@@ -1966,6 +1966,103 @@ def cell_hulls(ids, stats):
             "shape": (h, w)}
 
 
+# ---- nearest-cell transform, label expansion and cell contacts (neighbors.hip) ----------------------
+CONTACTS_FIRST_CAPACITY = 4096
+
+
+def nearest_site(ids):
+    """The feature transform of a label map (include/eunet.h, "nearest-cell transform, label expansion and cell
+    contacts"): ids [h, w] or [p, h, w], int32 or int64, contiguous, on the device -> (dist, site), int32 tensors shaped
+    as ids.  The sites of a plane are its pixels with id >= 1; dist is the exact squared Euclidean distance to the
+    nearest site of the own plane and site that site's linear index y w + x, the smallest index among the sites at the
+    minimum distance.  A plane without a site holds EDT_NONE and -1.  h, w <= 8192.  No synchronisation."""
+    name = "nearest_site"
+    ids = _id_maps(name, "ids", ids)
+    p, h, w = _plane_shape(name, "ids", ids.shape, False)
+    dist = torch.empty(ids.shape, dtype=torch.int32, device=ids.device)
+    site = torch.empty(ids.shape, dtype=torch.int32, device=ids.device)
+    # the column pass reads the ids and writes and re-reads the plane of rows; the row pass reads it and writes two
+    with kprof.timed(name, 0.0, float(p * h * w * (ids.element_size() + 6 * 4))):
+        call("eunet_nearest_site", _ptr(ids), ids.element_size(), p, h, w, _ptr(dist), _ptr(site), _stream())
+    return dist, site
+
+
+def expand_label_map(ids, distance=None, out=None):
+    """skimage.segmentation.expand_labels with a stated tie rule (include/eunet.h, eunet_expand_label_map): ids as for
+    nearest_site -> a tensor of ids' dtype and shape.  A pixel with an id other than 0 keeps it (negative "ignore"
+    ids too, which are no sites and are never overwritten); a pixel with id 0 takes the id of nearest_site's site when
+    its squared distance is <= floor(distance^2), and stays 0 otherwise.  distance None: no limit, the discrete
+    Voronoi partition of every plane that has a label.  out: the buffer to write, not ids itself.  (ops.expand_labels
+    is the instance unit's label map -> mask stack.)  No synchronisation."""
+    import math
+    name = "expand_label_map"
+    ids = _id_maps(name, "ids", ids)
+    p, h, w = _plane_shape(name, "ids", ids.shape, False)
+    if distance is None:
+        limit2 = -1
+    else:
+        try:
+            d = float(distance)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: distance must be None or a number, got {distance!r}") from None
+        if math.isnan(d) or d < 0.0:
+            raise ValueError(f"{name}: distance must be None or >= 0, got {distance!r}")
+        # beyond the longest distance of an 8192 x 8192 map every limit is "no smaller than any distance"
+        limit2 = int(math.floor(d * d)) if d < 2.0 ** 15 else 2 ** 31 - 2
+    if out is None:
+        out = torch.empty_like(ids)
+    else:
+        _out_buffer(name, "", out, ids.shape, ids.dtype, ids.device)
+        if out.data_ptr() == ids.data_ptr():
+            raise ValueError(f"{name}: out must not be ids itself")
+    ws = torch.empty(ids.shape, dtype=torch.int32, device=ids.device)
+    with kprof.timed(name, 0.0, float(p * h * w * (3 * ids.element_size() + 3 * 4))):
+        call("eunet_expand_label_map", _ptr(ids), ids.element_size(), p, h, w, limit2, _ptr(ws), _ptr(out), _stream())
+    return out
+
+
+def label_contacts(ids, connectivity: int = 4, _table_capacity=None):
+    """The sparse adjacency table of one label map (include/eunet.h, eunet_label_contacts): ids [h, w] or [p, h, w],
+    int32 or int64, contiguous, on the device -> numpy int64 [m, 4] of rows (plane, a, b, n), a < b, sorted
+    lexicographically: n adjacent pixel pairs of the plane carry the ids a and b.  connectivity 4 pairs a pixel with
+    its right and lower neighbour (n = the unit pixel sides the two labels share), 8 also with the two lower diagonal
+    ones.  Ids 0 and below take no part.  Ids reach 2^24 - 1; a larger one raises ValueError.  The table is read
+    back: the call synchronises.  _table_capacity: the first size of the hash table (a power of two; it is doubled
+    until every row fits), for tests."""
+    import numpy as np
+    name = "label_contacts"
+    ids = _id_maps(name, "ids", ids)
+    p, h, w = _plane_shape(name, "ids", ids.shape, False)
+    if connectivity not in (4, 8):
+        raise ValueError(f"{name}: connectivity must be 4 or 8, got {connectivity!r}")
+    cap = _table_cap(name, _table_capacity) or CONTACTS_FIRST_CAPACITY
+    dev = ids.device
+    nbytes = float(p * h * w * ids.element_size())
+
+    def contacts(cap):
+        # one int64 buffer: the keys, then [cap] the invalid count, then the int32 counts and [cap] the overflow
+        buf = torch.empty(cap + 1 + (cap + 2) // 2, dtype=torch.int64, device=dev)
+        vals = buf[cap + 1:].view(torch.int32)
+        with kprof.timed(name, 0.0, nbytes):
+            call("eunet_label_contacts", _ptr(ids), ids.element_size(), p, h, w, int(connectivity), _ptr(buf),
+                 _ptr(vals), cap, _ptr(vals[cap:]), _ptr(buf[cap:]), _stream())
+        host = buf.cpu().numpy()  # the one copy to the host
+        k, invalid = host[:cap], int(host[cap])
+        v = host[cap + 1:].view(np.int32)
+        if invalid:
+            raise ValueError(f"{name}: {invalid} pixel(s) hold an id above 2^24 - 1")
+        return v[cap], (k, v)
+
+    cap, (k, v) = _fill_table(name, "contact", cap, contacts)
+    used = k != -1
+    k, n = k[used].view(np.uint64), v[:cap][used].astype(np.int64)  # unsigned: a plane above 32767 sets the top bit
+    order = np.argsort(k, kind="stable")  # plane, a, b are the key's fields from the top: key order is row order
+    k, n = k[order], n[order]
+    mask = np.uint64(_lib.PAIRS_MAX_ID)
+    fields = [k >> np.uint64(48), (k >> np.uint64(24)) & mask, k & mask]
+    return np.stack([f.astype(np.int64) for f in fields] + [n], axis=1).reshape(-1, 4)
+
+
 # ---- dual-branch fusion (fusion.hip) -------------------------------------------------
 def fusion_tiles(n, h, w):
     t, gt = c_int(), c_int()

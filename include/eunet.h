@@ -812,6 +812,45 @@ int eunet_cell_hulls(const void* ids, int elem_bytes, int p, int h, int w, int n
                      const int32_t* row_y0, int32_t* ext, int32_t* verts, int64_t* hull, int64_t* outside,
                      void* stream);
 
+/* ---- nearest-cell transform, label expansion and cell contacts (neighbors.hip) ------------------
+ * No reference line: the reference counts cells and relates none to another.  This comment is the definition.
+ * ids are p planes of h x w ids, int32 or int64 (elem_bytes 4 or 8), as for eunet_cell_stats.  With x the column and
+ * y the row of a pixel, its linear index in its plane is y w + x.
+ * eunet_nearest_site: the feature transform.  The sites of a plane are its pixels with id >= 1; ids <= 0 are not
+ *   sites.  dist int32 [p][h][w] = the exact squared Euclidean distance of every pixel to the nearest site of its own
+ *   plane, site int32 [p][h][w] = the linear index of that site.  Tie rule: among the sites at the minimum distance the
+ *   one of smallest linear index wins, so (dist, site) is the lexicographic minimum of (d^2, index) over all sites of
+ *   the plane.  A site is its own nearest site (0, own index).  A plane without a site holds EUNET_EDT_NONE and -1.
+ *   Two kernels: a column pass (one thread per column, the row of the nearest site of the own column, the smaller row
+ *   among two equally near, -1 without one) and a row pass (one block per row, scanning outward from r = 0 and
+ *   stopping at the first r with r^2 > best, strictly: a candidate at r^2 == best in the pixel's own row ties the
+ *   best and may have the smaller index).  The column pass leaves its rows in site, the row pass works in place.
+ * eunet_expand_label_map: skimage.segmentation.expand_labels with the tie rule above (the name eunet_expand_labels
+ *   is the instance unit's label map -> mask stack).  out has the element size and shape of ids and must not overlap
+ *   them.  out(x) = ids(x) where ids(x) != 0: negative ids ("ignore") are kept and never overwritten, and they are no
+ *   sites.  Elsewhere out(x) = ids(site(x)) when dist(x) <= limit2 and 0 otherwise; a plane without a site stays 0
+ *   where it was 0.  limit2 = floor(distance^2), formed by the caller in 64 bits; limit2 < 0 means no limit, the
+ *   discrete Voronoi partition of the plane.  ws int32 [p][h][w] is the column pass's output; the row pass gathers
+ *   the id while it still holds the winner and scans no further than r^2 <= limit2.
+ * eunet_label_contacts: the sparse adjacency table of one id map.  Connectivity 4: every pixel is paired with its
+ *   right and its lower neighbour; connectivity 8: also with its lower-left and lower-right neighbour, so every
+ *   unordered pair of adjacent pixels is seen once.  A pair carrying two different ids >= 1 adds 1 to the count of the
+ *   key (plane, min id, max id); 0 and negative ids take no part.  At connectivity 4 a count is the number of unit
+ *   pixel sides the two labels share.  An id above EUNET_PAIRS_MAX_ID on any pixel is counted in *invalid (device
+ *   int64) and takes no part.  keys, counts, capacity, overflow: the open-addressing table of eunet_label_pairs with
+ *   the key plane << 48 | min << 24 | max, cleared by the call together with *invalid; when *overflow != 0 the table
+ *   is incomplete and the call is repeated with a larger one.  One pass; a run of equal keys along a row within 256
+ *   pixels inserts once, with its length.
+ * Every value is an integer and does not depend on the order of evaluation: two runs give identical bits.  Limits
+ * are eunet_edt_sq's: 1 <= h, w <= EUNET_EDT_MAX_SIDE, 1 <= p <= 65535.  ids and out aligned to elem_bytes, the int32
+ * arrays to 4 and the int64 ones to 8 bytes.  No host synchronisation, no allocation. */
+int eunet_nearest_site(const void* ids, int elem_bytes, int p, int h, int w, int32_t* dist, int32_t* site,
+                       void* stream);
+int eunet_expand_label_map(const void* ids, int elem_bytes, int p, int h, int w, long long limit2, int32_t* ws,
+                           void* out, void* stream);
+int eunet_label_contacts(const void* ids, int elem_bytes, int p, int h, int w, int connectivity, int64_t* keys,
+                         int32_t* counts, long long capacity, int32_t* overflow, int64_t* invalid, void* stream);
+
 /* ---- signed distance maps and the boundary loss (sdf.hip) ---------------------------
  * No reference line to cite: every loss of the reference is a region loss.  The boundary loss of Kervadec et al.,
  * "Boundary loss for highly unbalanced segmentation" (MIDL 2019), integrates the class probability against the
